@@ -2,7 +2,12 @@
 """Headline benchmark: 128x128 patches/sec of the full RCOT minimax iteration (critic step +
 gradient-penalty step + generator step, 3 optimizer steps) on the hand-written HIP path.
 
-  python bench.py --gpus N --steps K --warmup W [--config 2|3|5] [--prec fp32|bf16x3]
+  python bench.py --gpus N --steps K --warmup W [--config 2|3|5] [--prec fp32|bf16x3] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line (value, ms_per_step, losses of the last step).
+`--full` adds everything else it measures: the host enqueue time of one step, the roofline pass with the other two arithmetics
+timed beside it, the collective timings of data-parallel runs and the CPU baseline (`--no-roofline` / `--no-cpu-baseline` drop
+parts of it).  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 
 N > 1: when the process was not started by torch.distributed.run (no WORLD_SIZE in the environment) bench.py starts its own
 ranks — it re-executes itself under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` on
@@ -185,6 +190,38 @@ def launch_check(args, world, rank):
     return 0 if ok else 1
 
 
+DUMP_SAMPLE = 1 << 20          # elements kept of each flat parameter buffer (fixed seeded sample)
+DUMP_MAX_OUT = 4 << 20         # the generated batch is written whole up to this many elements, else as a seeded sample
+
+
+def _seeded_sample(t, n, seed):
+    """``t`` as float32 numpy: whole when it has at most ``n`` elements, else the flat elements at ``n`` sorted seeded indices"""
+    import numpy as np
+    t = t.detach()
+    if t.numel() <= n:
+        return t.float().cpu().numpy()
+    idx = np.sort(np.random.Generator(np.random.PCG64(seed)).integers(0, t.numel(), n))
+    return t.reshape(-1).index_select(0, torch.from_numpy(idx).to(t.device)).float().cpu().numpy()
+
+
+def dump_outputs(path, out, losses, Tn, Fn):
+    """What one timed step hands its caller, after the last timed step: the transport map's output batch (generated.npy,
+    [B,3,P,P] float32), the four logged losses (losses.npy, float64: Loss_F, Loss_T, Loss_mse, gp) and the parameters both
+    optimizer steps left (tnet_params.npy / fnet_params.npy: seeded samples of the flat parameter buffers).  Rank 0's view.
+    The inputs are the same in every run with the same arguments; the results are not bit for bit (some kernels accumulate with
+    atomics): two runs of one build at the headline workload differ by ~1e-4 in the generated batch and by up to ~1e-2 in
+    critic parameters whose gradients are rounding noise (RMSprop steps them by about the learning rate whatever their size)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"generated": _seeded_sample(out, DUMP_MAX_OUT, 11),
+              "losses": np.array([losses[k] for k in ("Loss_F", "Loss_T", "Loss_mse", "gp")], dtype=np.float64),
+              "tnet_params": _seeded_sample(Tn.store.flat[:Tn.store.layout.n_live], DUMP_SAMPLE, 12),
+              "fnet_params": _seeded_sample(Fn.store.flat[:Fn.store.layout.n_live], DUMP_SAMPLE, 13)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    log(f"outputs of the last timed step written to {path}: {', '.join(f'{k} {v.shape}' for k, v in arrays.items())}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -193,12 +230,15 @@ def main():
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS), help="BASELINE workload (see module docstring)")
     ap.add_argument("--prec", default=os.environ.get("RCOT_GEMM_PREC", "fp32"), choices=["fp32", "bf16x6", "bf16x3"],
                     help="arithmetic of the top-level value: fp32 (default, the product's default and the reference's arithmetic: exact fp32 "
-                         "MFMA), bf16x6 (fp32-class results from the bf16 pipe) or bf16x3; the other two are timed in the same run with the "
-                         "same number of steps and reported under extra.other_prec")
+                         "MFMA), bf16x6 (fp32-class results from the bf16 pipe) or bf16x3; with --full the other two are timed in the same run "
+                         "with the same number of steps and reported under extra.other_prec")
     ap.add_argument("--batch", type=int, default=0, help="override patches per GPU")
     ap.add_argument("--patch", type=int, default=0, help="override patch size")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure the host enqueue time, the roofline pass with "
+                                                        "the other arithmetics, the collectives and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="(--full) skip the roofline pass and the other arithmetics")
     ap.add_argument("--spawn", action="store_true", help="start the ranks through the self-launcher even for --gpus 1")
     ap.add_argument("--launch-check", action="store_true", help="rendezvous + one all-reduce only (no kernels; works on CPU with gloo)")
     ap.add_argument("--backend", default=None, choices=["nccl", "gloo"], help="process-group backend of --launch-check")
@@ -252,7 +292,9 @@ def main():
 
     def step(i, eager=False):
         x, y = batches[i % nb]
-        (st.iteration if eager else st.run)(x, y, de_dev, alphas[i % nb], cfg["paired"])
+        return (st.iteration if eager else st.run)(x, y, de_dev, alphas[i % nb], cfg["paired"])
+
+    last = {}
 
     def timed_run(steps, first):
         torch.cuda.synchronize()
@@ -261,7 +303,7 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for i in range(steps):
-            step(first + i)
+            last["out"] = step(first + i)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -281,19 +323,23 @@ def main():
     dt = timed_run(args.steps, args.warmup)
     losses = st.scalars()
     log(f"timed {args.steps} steps: {dt / args.steps * 1e3:.1f} ms/step")
-    torch.cuda.synchronize()
-    th = time.perf_counter()
-    step(args.warmup + args.steps)
-    host_ms = (time.perf_counter() - th) * 1e3          # time to ENQUEUE one step (GPU runs behind)
-    torch.cuda.synchronize()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["out"], losses, Tn, Fn)
     plans = st.planned is not None and st.planned.enabled
     mode = "eager launches from a recorded launch plan" if plans else "eager launches, Python schedule"
-    log(f"host enqueue time of one step: {host_ms:.1f} ms ({mode})")
-
-    # ---- per-kernel timing pass (HIP events on the launch stream) -> roofline of the dominant KERNEL SYMBOL, in both arithmetics
-    roof, extra = None, {"host_enqueue_ms_per_step": round(host_ms, 1), "launch_mode": mode}
+    roof, extra = None, {"launch_mode": mode}
     if plans:
         extra["plan_launches"] = [e["plan"].n_launches for e in st.planned.cache.values()]
+    if args.full:
+        torch.cuda.synchronize()
+        th = time.perf_counter()
+        step(args.warmup + args.steps)
+        host_ms = (time.perf_counter() - th) * 1e3          # time to ENQUEUE one step (GPU runs behind)
+        torch.cuda.synchronize()
+        log(f"host enqueue time of one step: {host_ms:.1f} ms ({mode})")
+        extra = {"host_enqueue_ms_per_step": round(host_ms, 1), **extra}
+
+    # ---- per-kernel timing pass (HIP events on the launch stream) -> roofline of the dominant KERNEL SYMBOL, in both arithmetics
     scale = (P / 128.0) ** 2
     ARITH = {"fp32": "fp32 MFMA 32x32x2 (exact: the reference's arithmetic)",
              "bf16x6": "bf16x6: weight projections as six bf16 partial products of a three-term split (fp32-class: as close to fp64 as the "
@@ -516,7 +562,7 @@ def main():
         ex["tnet_fwd_bwd_hbm_frac"] = r["path"]["hbm_frac"]
         return r, ex
 
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         roof, ex = measure_roofline(args.prec)
         extra.update(ex)
         log(f"roofline pass done ({args.prec}): {roof['kernel']} {roof['share_of_gpu_time']:.3f} of GPU time, frac {roof['frac']}; "
@@ -538,7 +584,7 @@ def main():
 
     # ---- data-parallel runs: what the collectives cost (one eagerly launched iteration, events on the reducer's side stream)
     comm = None
-    if dist.is_initialized():
+    if args.full and dist.is_initialized():
         comm = {"backend": dist.get_backend(), "ranks": dist.get_world_size(),
                 "rccl": ".".join(str(v) for v in torch.cuda.nccl.version()) if dist.get_backend() == "nccl" else None,
                 "allreduce_per_half_step": st.time_collectives(lambda: step(0, eager=True)),
@@ -546,7 +592,7 @@ def main():
 
     # ---- CPU baseline: the oracle's iteration on the host cores (rank 0, N=1 only; bounded sample, own process)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(cfg, lr)
 
     if rank == 0:

@@ -1,10 +1,10 @@
-# round-over-round on ONE box: the default bench (all three arithmetics in one run) from another checkout of the repository (e.g. the
+# round-over-round on ONE box: the full bench (all three arithmetics in one run; --full where bench.py has it) from another checkout of the repository (e.g. the
 # previous round's tree unpacked and built under build_variants/) and from this tree, alternately, inside one gpurun call
 #   bash scripts/ab_trees.sh build_variants/r05tree
 OLD=$1
 for rep in 1 2 3; do
   for tree in $OLD .; do
-    (cd $tree && python bench.py --no-cpu-baseline --steps 20 --warmup 5 2>/dev/null | tail -1 | python -c "
+    (cd $tree && python bench.py $(grep -qs -- '"--full"' bench.py && echo --full) --no-cpu-baseline --steps 20 --warmup 5 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 o = d['extra']['other_prec']

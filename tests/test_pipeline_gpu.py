@@ -230,8 +230,8 @@ def test_bench_through_its_own_launcher_with_rccl():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(RCOT_FORCE_REDUCER="1", PYTHONPATH=ROOT)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--spawn", "--steps", "2", "--warmup", "1",
-                        "--batch", "2", "--patch", "64", "--no-cpu-baseline", "--no-roofline"], capture_output=True, text=True,
-                       timeout=800, env=env)
+                        "--batch", "2", "--patch", "64", "--full", "--no-cpu-baseline", "--no-roofline"], capture_output=True,
+                       text=True, timeout=800, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["value"] > 0
@@ -239,3 +239,32 @@ def test_bench_through_its_own_launcher_with_rccl():
     assert comm["backend"] == "nccl" and comm["ranks"] == 1
     halves = comm["allreduce_per_half_step"]
     assert set(halves) == {"F_critic", "F_gp", "T_gen"} and all(h["buckets"] >= 1 and h["ms"] > 0 for h in halves.values())
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """`python bench.py --dump-outputs DIR` without --full: the result line carries the headline only (no roofline, no CPU
+    baseline), and DIR holds what the last timed step computed — the generated batch, the four losses of the line, and seeded
+    samples of both parameter buffers — in float32 / float64, within 64 MB."""
+    import json
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "RCOT_FORCE_REDUCER")}
+    env.update(PYTHONPATH=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2",
+                        "--patch", "64", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=500, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["comm"] is None
+    files = sorted(os.listdir(tmp_path))
+    assert files == ["fnet_params.npy", "generated.npy", "losses.npy", "tnet_params.npy"], files
+    assert sum(os.path.getsize(tmp_path / f) for f in files) <= 64 << 20
+    gen = np.load(tmp_path / "generated.npy")
+    assert gen.dtype == np.float32 and gen.shape == (2, 3, 64, 64) and np.isfinite(gen).all()
+    losses = np.load(tmp_path / "losses.npy")
+    assert losses.dtype == np.float64 and losses.shape == (4,)
+    want = line["losses_last_step"]
+    for v, k in zip(losses, ("Loss_F", "Loss_T", "Loss_mse", "gp")):
+        assert abs(v - want[k]) <= 1e-6 + 1e-6 * abs(want[k]), (k, v, want[k])
+    for name in ("tnet_params", "fnet_params"):
+        a = np.load(tmp_path / f"{name}.npy")
+        assert a.dtype == np.float32 and a.ndim == 1 and 0 < a.size <= 1 << 20 and np.isfinite(a).all(), name
