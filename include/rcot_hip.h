@@ -158,7 +158,7 @@ int rcot_gemm_kmajor(const float* At, long lda, long sAo, long sAi, int a_rows, 
  * `d`: HOST array of n descriptors (copied at the call), fields as the arguments of rcot_gemm_kmajor.  prec: RCOT_PREC_FP32 or
  * RCOT_PREC_BF16X6 (both run these products on the exact-fp32 kernel); RCOT_EUNSUPPORTED for RCOT_PREC_BF16X3 (nothing launched:
  * call rcot_gemm_kmajor per product).  ONE tile shape serves the grid — the one rcot_gemm_kmajor would choose for product 0 — and the
- * eight-wavefront k-group kernel is never used: a product with K < 512 (RCOT_XX_KG_MINK; every MDTA product: K = c or C <= 384) is
+ * eight-wavefront k-group kernel is never used: a product with K < 512 (every MDTA product: K = c or C <= 384) is
  * bit-identical to its own rcot_gemm_kmajor launch (the per-element summation order of gemm_xx_kernel does not depend on the tile);
  * with K >= 512 on <= 512 workgroups the single launch runs gemm_xx_kg_kernel, which adds two partial chains: equal to fp32
  * rounding, not to the bit. */

@@ -820,14 +820,13 @@ __global__ __launch_bounds__(256) void conv_wgrad_lean_kernel(GemmDims d, const 
     }
 }
 
-// 64 < rows <= 80 of the forward product and the weight gradient in one workgroup, sixteen at a time (RCOT_CONV_R16=0: A/B switch)
-// RCOT_CONV_R16 (bit mask, default 3 = both): bit 0 = 65..80 rows as five groups of sixteen; bit 1 = 17..32 / 33..48 rows as two / three groups
-// (the 24- and 48-channel resampling convolutions of the Restormer map, which ride in a 64-row tile: A/B switch, see NOTES round 6)
+// rows of the forward product and the weight gradient in one workgroup, sixteen at a time: 65..80 rows as five groups of sixteen;
+// 17..32 / 33..48 rows as two / three groups (the 24- and 48-channel resampling convolutions of the Restormer map, which would
+// otherwise ride in a 64-row tile; NOTES round 6)
 int conv_r16(int M) {
-    static const int mask = getenv("RCOT_CONV_R16") ? atoi(getenv("RCOT_CONV_R16")) : 3;
-    if ((mask & 1) && M > 64 && M <= 80) return 5;
-    if ((mask & 2) && M > 16 && M <= 32) return 2;
-    if ((mask & 2) && M > 32 && M <= 48) return 3;
+    if (M > 64 && M <= 80) return 5;
+    if (M > 16 && M <= 32) return 2;
+    if (M > 32 && M <= 48) return 3;
     return 0;
 }
 bool conv_rows80(int M) { return conv_r16(M) == 5; }
@@ -867,9 +866,8 @@ int launch_conv_wgrad_lean(GemmDims d, const float* dY, const ConvGeom& g, const
 
 int launch_conv_fwd_lean(GemmDims d, const float* Wt, const ConvGeom& g, const EpiP& ep, hipStream_t st) {
     // 128-row tiles where the 64-row plan has >= 1024 workgroups (measured per layer at B = 16: +3..9 % there, -7..-12 % below)
-    static const int tm2 = getenv("RCOT_CONV_LEAN_TM") ? atoi(getenv("RCOT_CONV_LEAN_TM")) : 0;
-    const bool two = tm2 != 1 && (d.M % 128) == 0 && ((long)cdiv(d.M, 64) * cdiv(d.N, 64) * d.S >= 1024 || tm2 == 2);
-    // 64 < M <= 80 (the 80-channel level of the MPRNet transport map): all rows in one workgroup, sixteen at a time (RCOT_CONV_R16=0: A/B)
+    const bool two = (d.M % 128) == 0 && (long)cdiv(d.M, 64) * cdiv(d.N, 64) * d.S >= 1024;
+    // 64 < M <= 80 (the 80-channel level of the MPRNet transport map): all rows in one workgroup, sixteen at a time
     const int r16 = conv_r16(d.M);
     const bool rows80 = r16 == 5;
     d.tilesM = r16 ? 1 : cdiv(d.M, two ? 128 : 64);

@@ -846,8 +846,7 @@ inline LaunchPlan plan_gemm(int M, int N, int K, int Z, bool allow_split, size_t
     p.S = 1;
     if (allow_split) {
         const int nkt = cdiv(K, BK);
-        // (RCOT_SPLIT_BLOCKS: tuning knob — the grid size a split aims at; default 768 = three workgroups per CU)
-        static const long target = getenv("RCOT_SPLIT_BLOCKS") ? atol(getenv("RCOT_SPLIT_BLOCKS")) : 768;
+        constexpr long target = 768;           // the grid size a split aims at: three workgroups per CU
         long S = (target + blocks - 1) / blocks;
         if (S > nkt / 2) S = nkt / 2;          // keep >= 2 K-tiles per split
         if (S < 1) S = 1;

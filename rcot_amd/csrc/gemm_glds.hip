@@ -713,7 +713,7 @@ int rcot_gemm_kmajor(const float* At, long lda, long sAo, long sAi, int a_rows, 
     p.ep.alpha = 1.f; p.ep.beta = beta; p.ep.lrelu = 1.f;
     const int Z = Zo * Zi;
     {   // streaming stores when the output is larger than the L2s can hold for its consumer (and nothing is accumulated into it)
-        static const long mb = getenv("RCOT_XX_NTS_MB") ? atol(getenv("RCOT_XX_NTS_MB")) : 32;     // (read once, like every other switch here)
+        static const long mb = getenv("RCOT_XX_NTS_MB") ? atol(getenv("RCOT_XX_NTS_MB")) : 32;     // (read once)
         p.ep.nts = (mb > 0 && beta == 0.f && 4L * M * N * Z >= (mb << 20)) ? 1 : 0;
     }
     // RCOT_PREC_BF16X1: the split-bf16 kernels and packs of RCOT_PREC_BF16X3 with the hi * hi product alone (EpiP::one)
@@ -722,14 +722,13 @@ int rcot_gemm_kmajor(const float* At, long lda, long sAo, long sAi, int a_rows, 
         prec = RCOT_PREC_BF16X3;
         p.ep.one = 1;
     }
-    static const bool xx_ln_comp = !(getenv("RCOT_XX_LN_COMP") && atoi(getenv("RCOT_XX_LN_COMP")) == 0);
     if (ln_compute && prec == RCOT_PREC_FP32) {
         // exact fp32: gemm_xx_kernel makes the statistics of its pixel columns itself (XXP::ln_comp), in ln_stats_kernel's arithmetic
         // planes above 64x64 keep the rcot_ln_stats launch: there the workgroups' own pass over their column panel costs more than
         // the launch it replaces (a 128x128 block forward 553 -> 579 us, profiles/r05_ab_small_levels.txt); below, the two are equal
         // in time (145.8 vs 145.8 us at 32x32) and the projection is one launch less to enqueue
-        static const int xx_ln_maxn = getenv("RCOT_XX_LN_MAXN") ? atoi(getenv("RCOT_XX_LN_MAXN")) : 4096;
-        if (!ln || !xx_ln_comp || N > xx_ln_maxn || (sLN & 3) || !al16(ln_mu) || !al16(ln_rs) || (ldb & 3)) return RCOT_EUNSUPPORTED;
+        constexpr int xx_ln_maxn = 4096;
+        if (!ln || N > xx_ln_maxn || (sLN & 3) || !al16(ln_mu) || !al16(ln_rs) || (ldb & 3)) return RCOT_EUNSUPPORTED;
         p.ln_comp = 1;
         p.mu_out = ln_mu; p.rs_out = ln_rs;
     } else if (ln_compute) {
@@ -737,7 +736,7 @@ int rcot_gemm_kmajor(const float* At, long lda, long sAo, long sAi, int a_rows, 
         if (!ln || !AtF || !ln_c12 || !Asplit) return RCOT_EUNSUPPORTED;
         const int rcw = try_gemm_kmajor_x3w(AtF, lda, sAo, sAi, Asplit, Bm, ldb, sBo, sBi, p.ep, ln_mu, ln_rs, sLN, ln_c12,
                                             ln_c12 + ((M + 3) & ~3), Zo, Zi, M, N, K, ws, ws_bytes, (hipStream_t)stream, true,
-                                            prec == RCOT_PREC_BF16X6 ? 3 : (prec == RCOT_PREC_BF16X3 ? 2 : 1));
+                                            prec == RCOT_PREC_BF16X6 ? 3 : 2);
         return rcw == -100 ? RCOT_EUNSUPPORTED : rcw;
     }
     if (prec == RCOT_PREC_BF16X6 && Asplit && (!ln || (AtF && ln_c12))) {
@@ -765,39 +764,20 @@ int rcot_gemm_kmajor(const float* At, long lda, long sAo, long sAi, int a_rows, 
                                           (hipStream_t)stream);
         if (rc != -100) return rc;
     }
-    // exact fp32 on the producer / consumer data path (x3p_kernel<.., NT = 1>: v_mfma_f32_32x32x2_f32 fed from the raw rings, LN fold
-    // and epilogue statistics as the split kernels) — OPT-IN (RCOT_F32_PC=1): measured equal to gemm_xx_kernel on average (510 <- 96
-    // + LN at 8 x 128x128: 160 vs 170 us, 1020 <- 192 at 32x32: 36 vs 41; 96 <- 510: 162 vs 135 — a single 128-row tile wastes a
-    // quarter of the MFMA work on 96 rows, and with the consumers MFMA-bound their epilogue stores no longer hide behind anything)
-    static const bool pc_f32 = getenv("RCOT_F32_PC") && atoi(getenv("RCOT_F32_PC")) == 1;
-    static const int pc_f32_maxn = getenv("RCOT_F32_PC_MAXN") ? atoi(getenv("RCOT_F32_PC_MAXN")) : 1 << 30;
-    if (pc_f32 && !p.ln_comp && N <= pc_f32_maxn && (!ln || (AtF && ln_c12))) {
-        const int rcw = try_gemm_kmajor_x3w(ln ? AtF : At, lda, sAo, sAi, nullptr, Bm, ldb, sBo, sBi, p.ep, ln_mu, ln_rs, sLN,
-                                            ln ? ln_c12 : nullptr, ln ? ln_c12 + ((M + 3) & ~3) : nullptr, Zo, Zi, M, N, K, ws, ws_bytes,
-                                            (hipStream_t)stream, false, 1);
-        if (rcw != -100) return rcw;
-    }
     const long pad96 = (long)cdiv(M, 96) * 96, pad128 = (long)cdiv(M, 128) * 128;
     const long big_tiles = (long)cdiv(M, 128) * (N / 128) * Z;
-    static const int force_tile = getenv("RCOT_XX_TILE") ? atoi(getenv("RCOT_XX_TILE")) : 0;     // tuning: 64 / 96 / 128 forces the tile
-    if (force_tile == 64 || (force_tile && (N % 128))) return launch_xx<64, 64, 2, 2>(p, ln, Z, (hipStream_t)stream);
-    if (force_tile == 96) return launch_xx<96, 128, 1, 4>(p, ln, Z, (hipStream_t)stream);
-    if (force_tile == 128) return launch_xx<128, 128, 2, 2>(p, ln, Z, (hipStream_t)stream);
     if ((N % 128) == 0 && big_tiles >= 192) {
         // M <= 64 (the 48-channel level: 48 <- 48 / 127 / 144 / 254): a 64-row tile on 1 x 4 wavefronts — a third less MFMA work than the 96-row
-        // tile these products rode in through round 5 (half of whose rows they left empty); same bits (round 6, RCOT_XX_M64=0 for the A/B)
-        static const bool m64 = !(getenv("RCOT_XX_M64") && atoi(getenv("RCOT_XX_M64")) == 0);
-        if (m64 && M <= 64) return launch_xx<64, 128, 1, 4>(p, ln, Z, (hipStream_t)stream);
+        // tile these products rode in through round 5 (half of whose rows they left empty); same bits (round 6)
+        if (M <= 64) return launch_xx<64, 128, 1, 4>(p, ln, Z, (hipStream_t)stream);
         const bool w96 = pad96 < pad128;
         if (w96) return launch_xx<96, 128, 1, 4>(p, ln, Z, (hipStream_t)stream);
         return launch_xx<128, 128, 2, 2>(p, ln, Z, (hipStream_t)stream);
     }
     // long reductions on few workgroups (the data gradients of the 32x32 / 16x16 planes): the eight-wavefront k-group form
-    static const bool kg_on = !(getenv("RCOT_XX_KG") && atoi(getenv("RCOT_XX_KG")) == 0);
-    static const int kg_mink = getenv("RCOT_XX_KG_MINK") ? atoi(getenv("RCOT_XX_KG_MINK")) : 512;
-    static const int kg_maxwg = getenv("RCOT_XX_KG_MAXWG") ? atoi(getenv("RCOT_XX_KG_MAXWG")) : 512;
+    constexpr int kg_mink = 512, kg_maxwg = 512;     // measured: profiles/r05_ab_kg.txt
     const long wgs64 = (long)cdiv(M, 64) * (N / 64) * Z;
-    if (kg_on && !ln && K >= kg_mink && wgs64 <= kg_maxwg) {
+    if (!ln && K >= kg_mink && wgs64 <= kg_maxwg) {
         p.tilesM = cdiv(M, 64);
         p.tilesN = N / 64;
         const size_t smem = sizeof(float) * (size_t)KG_NST * BK * 128;
@@ -909,10 +889,9 @@ int rcot_gemm_kmajor_multi(const rcot_kmajor_desc* d, int n, int N, int prec, vo
         RCOT_LAUNCH((gemm_xx_multi_kernel<BM, BN, WM, WN>), dim3(total), dim3(GEMM_NT), smem, st, P);                 \
     } while (0)
     if ((N % 128) == 0 && big_tiles >= 192) {
-        static const bool m64 = !(getenv("RCOT_XX_M64") && atoi(getenv("RCOT_XX_M64")) == 0);
         int mmax = 0;
         for (int i = 0; i < n; ++i) mmax = P.q[i].M > mmax ? P.q[i].M : mmax;
-        if (m64 && mmax <= 64) RCOT_XX_MULTI(64, 128, 1, 4);
+        if (mmax <= 64) RCOT_XX_MULTI(64, 128, 1, 4);
         else if (pad96 < pad128) RCOT_XX_MULTI(96, 128, 1, 4);
         else RCOT_XX_MULTI(128, 128, 2, 2);
     } else {

@@ -141,8 +141,6 @@ int nt_configure(int M, int N, int K, int Zo, int Zi, const float* A, long lda, 
         (sBk & 3) || !a16(A) || !a16(B) || (Kb && (Kb & 15)) || Z > 16384)
         return -100;
     if (mu && ((sLNb & 3) || !a16(mu) || !a16(rs))) return -100;
-    static const bool old_gate = getenv("RCOT_NT_OLD") != nullptr;     // debugging: the round-1 gate
-    if (old_gate && (M < 96 || N < 96)) return -100;
     if (M < 33 || N < 33) return -100;                 // 64- or 128-row DMA images: tiny channel counts stay on the 64x64 engine
     NTP p{};
     p.M = M; p.N = N; p.K = K; p.Zi = Zi;
@@ -163,14 +161,8 @@ int nt_configure(int M, int N, int K, int Zo, int Zi, const float* A, long lda, 
         const long area = (long)cdiv(M, cand_bm[c]) * cand_bm[c] * cdiv(N, cand_bn[c]) * cand_bn[c];
         if (best < 0 || area < best) { best = area; cfg = c; }
     }
-    // short reductions (the 16x16 / 32x32 levels: K = batch * pixels <= 8192): the product is a few microseconds of work and the
-    // slabs dominate (written once, read once by the reduce: 8 M N S bytes).  64 x 64 tiles need a quarter of the split factor
-    // of 128 x 128 tiles for the same number of workgroups: 4x fewer slab bytes for the kernel AND for the launch that sums them
-    // (rcot_block_param_reduce).  MEASURED (round 3): the 64 x 64 form runs the weight gradients of the 16x16 level in 20 / 45 / 26 us against
-    // 15 / 24 / 18 us for the 128-wide tiles with their larger split: NOT adopted, RCOT_NT_SMALLK=1 turns it on for A/B runs.
-    static const bool smallk = getenv("RCOT_NT_SMALLK") && atoi(getenv("RCOT_NT_SMALLK")) == 1;
-    const bool small = smallk && Z == 1 && K <= 8192 && (long)cdiv(M, 64) * cdiv(N, 64) >= 24;
-    if (small) cfg = 5;                                       // (off by default below: measured slower, see DESIGN)
+    // (forcing 64 x 64 tiles with a quarter of the split factor on the short reductions of the 16x16 / 32x32 levels measured slower,
+    // 20 / 45 / 26 us against 15 / 24 / 18 us, round 3: not adopted)
     const int bm = cand_bm[cfg], bn = cand_bn[cfg];
     const long tiles = (long)cdiv(M, bm) * cdiv(N, bn) * Z;
     const int nslab = K / BK;
@@ -178,18 +170,12 @@ int nt_configure(int M, int N, int K, int Zo, int Zi, const float* A, long lda, 
     // operand + slab (write once, read once) traffic
     const double flops = 2.0 * M * N * (double)K * Z;
     const double in_bytes = 4.0 * ((double)M * cdiv(N, bn) + (double)N) * K * Z;
-    static const int slots_env = getenv("RCOT_NT_SLOTS") ? atoi(getenv("RCOT_NT_SLOTS")) : 0;     // tuning: workgroup slots the split factor aims at
-    if (slots_env > 0 && slots == 640) slots = slots_env;
     long S = 1;
     double best_t = 1e30;
     for (long cand = 1; cand <= nslab / 4 && cand * Z <= 65535; cand *= 2) {
         const double eff = fmin(1.0, (double)(tiles * cand) / (double)slots);   // (slots: 640, half of it in a paired launch)
         const double t = flops / ((prec == 2 ? 2.0e14 : (prec ? 3.0e14 : 9.0e13)) * eff) + (in_bytes + 8.0 * M * N * (double)cand * Z) / 3.5e12;
         if (t < best_t) { best_t = t; S = cand; }
-    }
-    if (small) {                                              // fill ~640 workgroup slots, at least 8 slabs per piece
-        S = 1;
-        while (S * 2 * tiles <= slots && S * 2 <= nslab / 8) S *= 2;
     }
     const size_t per = (size_t)M * p.ldws * Z * sizeof(float);
     while (S > 1 && per * S > ws_bytes) --S;

@@ -1363,9 +1363,8 @@ int rcot_gdfn_gate_fwd(const float* p, const float* w, float* g, int B, int hid,
     }
     const long nq = (long)B * hid * (H >> 2) * (W >> 2);
     // the neighbour-lane form of the patch loads (all twelve rows of both planes requested before the first lane shift; with the
-    // loads inside per-row `if` blocks it measured SLOWER than the scalar-halo form, 33.8 vs 30.8 us); RCOT_GATE_NB=0 for A/B
-    static const bool gate_nb = !(getenv("RCOT_GATE_NB") && atoi(getenv("RCOT_GATE_NB")) == 0);
-    if (gate_nb && nb_lanes_ok(W))
+    // loads inside per-row `if` blocks it measured SLOWER than the scalar-halo form, 33.8 vs 30.8 us)
+    if (nb_lanes_ok(W))
         RCOT_LAUNCH(gate_fwd_kernel<true>, dim3(cdiv(nq, 256)), dim3(256), 0, (hipStream_t)stream, p, w, g, nq, hid, H, W);
     else
         RCOT_LAUNCH(gate_fwd_kernel<false>, dim3(cdiv(nq, 256)), dim3(256), 0, (hipStream_t)stream, p, w, g, nq, hid, H, W);

@@ -23,7 +23,6 @@ Two choices that are not the reference's op order (results equal up to fp32 roun
 """
 from __future__ import annotations
 
-import os
 from collections import OrderedDict
 from typing import Callable, Dict, List, Optional
 
@@ -116,16 +115,10 @@ class _CAB:
         be.row_scale_add(dout, gate, None, dmean, 1.0 / (H * W), dres)
         net._leaf(lambda: be.conv2d_wgrad(dres, a, self.gW2, 1, 1, 1.0), dres, a)
         da = be.empty(B, C, H, W)
-        if self.W2f is not None:                                     # the data gradient as a forward product with the flipped weight
-            be.conv2d_fwd(dres, self.W2f, None, da, 1, 1)
-        else:
-            be.conv2d_dgrad(dres, self.W2, da, 1, 1)
+        be.conv2d_fwd(dres, self.W2f, None, da, 1, 1)                # the data gradient as a forward product with the flipped weight
         be.prelu_bwd(da, c1, self.slope, da, self.gslope)
         net._leaf(lambda: be.conv2d_wgrad(da, x, self.gW0, 1, 1, 1.0), da, x)
-        if self.W0f is not None:
-            be.conv2d_fwd(da, self.W0f, None, dout, 1, 1, 1.0, 0, dout)      # + the residual's gradient (R = the output buffer)
-        else:
-            be.conv2d_dgrad(da, self.W0, dout, 1, 1, beta=1.0)
+        be.conv2d_fwd(da, self.W0f, None, dout, 1, 1, 1.0, 0, dout)          # + the residual's gradient (R = the output buffer)
         return dout
 
 
@@ -151,13 +144,12 @@ class MPRNetHip:
         # Flipped copies Wf[ci][co][2-ky][2-kx] of the 3x3 C -> C weights (44 tensors): with them a data gradient is a FORWARD product
         # (rcot_conv_weight_flip).  The forward kernel has a form for 64 < rows <= 80 (16 rows at a time; the data-gradient kernel computes
         # 128 rows for them: 158 -> 85 us per product at 4 x 128 x 128) and is the faster of the two at the other levels as well
-        # (128 channels at 64 x 64: 74 -> 65 us).  One launch per channel count; refreshed by repack().  RCOT_MPRNET_FLIP=0: A/B.
-        flip_on = os.environ.get("RCOT_MPRNET_FLIP", "1") != "0"
+        # (128 channels at 64 x 64: 74 -> 65 us).  One launch per channel count; refreshed by repack().
         self._flip_groups = []                                        # (C, names, table)
         self._flip_view: Dict[str, torch.Tensor] = {}
         names_by_c: Dict[int, List[str]] = {}
         for n, sh in uniq:
-            if flip_on and len(sh) == 4 and sh[2] == 3 and sh[0] == sh[1]:
+            if len(sh) == 4 and sh[2] == 3 and sh[0] == sh[1]:
                 names_by_c.setdefault(sh[0], []).append(n)
         total = sum(c * c * 9 * len(v) for c, v in names_by_c.items())
         self._flip = be.zeros(max(1, total))

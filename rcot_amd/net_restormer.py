@@ -21,18 +21,10 @@ from collections import OrderedDict
 from typing import Callable, Dict, List, Optional
 
 import numpy as np
-import os
 
 import torch
 
 from . import params as P
-
-# A/B switch (profiles/r05_ab_wgrad_after*.txt): a side-stream 1x1 weight gradient starts BEHIND its data gradient instead of with it
-# which of a block's three 1x1 weight gradients start BEHIND their data gradient instead of with it: bit 0 project_out, bit 1 project_in,
-# bit 2 qkv (A/B switch; "1" of round 5 = all three = 7)
-_WGRAD_AFTER = {"0": 0, "1": 7}.get(os.environ.get("RCOT_WGRAD_AFTER", "0"), None)
-if _WGRAD_AFTER is None:
-    _WGRAD_AFTER = int(os.environ["RCOT_WGRAD_AFTER"])
 
 
 # =============================================================================== parameter store
@@ -171,18 +163,10 @@ class TransformerBlockOp:
         if d is not None:
             slabs.append(d)
             return
-        if not getattr(be, "side_wgrad", True):
-            be.conv1x1_dgrad(W, dY, dX, packed=packed)
-            slabs.append(self._wgrad(dY, X, gW, ln, part))
-            return
         hold = (dY, X) + ((ln[0], ln[1]) if ln is not None else ())
         # (the weight gradient starts WITH its data gradient: started behind it — next to the bandwidth- / latency-bound kernels that follow
         # instead of next to another MFMA-bound product — it closes the block later: 77.2 -> 81.3 ms per iteration in exact fp32, 74.0 -> 76.5
         # in bf16x6, profiles/r05_ab_wgrad_after.txt)
-        if (_WGRAD_AFTER >> part) & 1:
-            be.conv1x1_dgrad(W, dY, dX, packed=packed)
-            be.side_run(lambda: slabs.append(self._wgrad(dY, X, gW, ln, part)), *hold)
-            return
         be.side_run(lambda: slabs.append(self._wgrad(dY, X, gW, ln, part)), *hold)
         be.conv1x1_dgrad(W, dY, dX, packed=packed)
 
@@ -348,6 +332,8 @@ class Conv3x3Op:
     """Dense 3x3 conv (pad 1, no bias) with optional PixelUnshuffle (cmap 1) / PixelShuffle (cmap 2)
     folded into the store — Net_Restormer.py:86-94, 103-111, 113-122, 326."""
 
+    PCM_MINC = 48       # fewest channels (in and out) the padded-plane products are used from
+
     def __init__(self, be, store, name, cmap=0):
         self.be, self.W, self.gW, self.cmap, self.name = be, store.p[name], store.g[name], cmap, name
         # bf16x3 arithmetic, channel counts that are multiples of 16 (the Down/Upsample convolutions from level 2 on): forward and
@@ -355,10 +341,8 @@ class Conv3x3Op:
         # ~55 of the implicit-GEMM engine at these shapes); the (un)shuffle then is its own small launch.  The transport map is
         # not the critic: its gradients keep their bars with split products (tests/test_iteration_grads_gpu.py).
         Co, Ci = self.W.shape[0], self.W.shape[1]
-        self._pcm = (hasattr(be, "conv_pcm_fwd") and os.environ.get("RCOT_TCONV_PCM", "1") != "0" and Ci % 16 == 0 and Co % 16 == 0
-                     and min(Ci, Co) >= int(os.environ.get("RCOT_TCONV_PCM_MINC", "48")))
+        self._pcm = hasattr(be, "conv_pcm_fwd") and Ci % 16 == 0 and Co % 16 == 0 and min(Ci, Co) >= self.PCM_MINC
         self._packs = None
-        self._pcm_wgrad = os.environ.get("RCOT_TCONV_PCM_WGRAD", "1") != "0"     # (A/B switch: weight gradient on the engine)
 
     def repack(self):
         """operand packs of the padded-plane products (after every parameter change; made at first use in bf16x3)"""
@@ -407,7 +391,7 @@ class Conv3x3Op:
             be.pixel_shuffle(dy, d, 2 if self.cmap == 1 else 1)     # inverse permutation
             dy = d
         pkw = self._pcm_packs(H, W)
-        prepped = pkw is not None and self._pcm_wgrad and be.conv_pcm_wgrad(dy, x, self.gW, 1.0)
+        prepped = pkw is not None and be.conv_pcm_wgrad(dy, x, self.gW, 1.0)
         if not prepped:
             be.conv2d_wgrad(dy, x, self.gW, 1, 1, beta=1.0)
         if not need_dx:
@@ -838,17 +822,10 @@ class F_net:
                                    gb=st.g.get(bn) if bias else None, s=s, pad=pad, cout=cout))
         self.n_live_gp = st.layout.offset["fc2.bias"]          # optimizer range of the GP step
         self._ctx = None
-        # RCOT_CONV_PCM=1 (opt-in, bf16x3 arithmetic only): the nine inner convolutions (Ci >= 64) and their data gradients as
-        # split-bf16 K-major products over padded channel-major operands (rcot_conv_pcm_*, csrc/conv_pcm.hip), ~2x the
-        # implicit-GEMM engine on those layers (-2.5 ms/step at B=8, 128x128).  NOT the default: each product is 5e-6 accurate,
-        # but the critic's LeakyReLU masks, the GP double backward and RMSprop's sign-like first steps amplify that past the
-        # gradient-parity bars of tests/test_iteration_grads_gpu.py (1 - cos of the GP gradients 5e-4..8e-4 vs 4e-4; DESIGN.md
-        # section 6), so the critic's convolutions stay exact fp32 in both arithmetics unless asked otherwise.
-        self._pcm = hasattr(be, "conv_pcm_fwd") and os.environ.get("RCOT_CONV_PCM", "0") == "1"
-        self._packs = {}
-        self._stale = True
-        self._mask_fold = os.environ.get("RCOT_MASK_FOLD", "1") != "0"      # (A/B switch: separate rcot_lrelu_bwd launches)
-        self._side_leaves = hasattr(be, "side_run") and os.environ.get("RCOT_F_SIDE", "1") != "0"
+        # The critic's convolutions are exact fp32 in every arithmetic: as split-bf16 padded-plane products (rcot_conv_pcm_*) each is
+        # 5e-6 accurate, but the LeakyReLU masks, the GP double backward and RMSprop's sign-like first steps amplify that past the
+        # gradient-parity bars of tests/test_iteration_grads_gpu.py (NOTES.md, retired switches).
+        self._side_leaves = hasattr(be, "side_run")
         #: called as hook(n_final) during backward(wgrad=True) when grad[0:n_final) of the flat buffer is final (the layout
         #: follows the critic-loss backward: fc2, fc1, fc, then the convolutions last to first)
         self.grad_ready_hook: Optional[Callable[[int], None]] = None
@@ -858,7 +835,7 @@ class F_net:
 
     def _leaf(self, fn, *hold):
         """a parameter-gradient product of the backward sweeps (nothing in the sweep reads its result): next to the data-gradient
-        chain on the backend's side stream (RCOT_F_SIDE=0: in line)"""
+        chain on the backend's side stream where it has one"""
         if self._side_leaves:
             self.be.side_run(fn, *hold)
         else:
@@ -876,34 +853,8 @@ class F_net:
             self.be.side_join()
             self.grad_tail_hook(self.store.layout.offset[from_param])
 
-    def _pcm_layer(self, li, H, W):
-        """the (forward, data-gradient) pack pair of conv ``li`` for an H x W input, or None (the layer runs on rcot_conv2d_*)"""
-        if not (self._pcm and getattr(self.be, "prec", 0) == 1):
-            return None
-        if self._stale:
-            self.repack()
-        cv = self.convs[li]
-        Co, Ci, k, _ = cv["W"].shape
-        if li in self._packs and self.be.conv_pcm_ok(Ci, Co, k, cv["s"], cv["pad"], H, W):
-            return self._packs[li]
-        return None
-
     def repack(self):
-        """pre-split packs of the inner conv weights in forward and data-gradient operand order (after every parameter change;
-        deferred to the next use while the exact-fp32 arithmetic is selected)"""
-        if not self._pcm:
-            return
-        if getattr(self.be, "prec", 0) != 1:
-            self._stale = True
-            return
-        self._stale = False
-        for li, cv in enumerate(self.convs):
-            Wt = cv["W"]
-            k = Wt.shape[2]
-            if Wt.shape[1] % 16 or Wt.shape[0] % 16 or (k, cv["s"], cv["pad"]) not in ((3, 1, 1), (4, 2, 1)):
-                continue
-            old = self._packs.get(li, (None, None))
-            self._packs[li] = (self.be.conv_pcm_pack(Wt, "fwd", old[0]), self.be.conv_pcm_pack(Wt, "dgrad", old[1]))
+        """nothing to do: the critic keeps no private copies of its weights (the networks' common interface)"""
 
     state_dict = T_net.state_dict
     load_state_dict = T_net.load_state_dict
@@ -927,11 +878,7 @@ class F_net:
             k = cv["W"].shape[2]
             OH, OW = (H + 2 * cv["pad"] - k) // cv["s"] + 1, (W + 2 * cv["pad"] - k) // cv["s"] + 1
             y = be.empty(B, cv["cout"], OH, OW)
-            pk = self._pcm_layer(len(acts) - 1, H, W)
-            if pk is not None:
-                be.conv_pcm_fwd(a, pk[0], cv["b"], y, k, 0.2)
-            else:
-                be.conv2d_fwd(a, cv["W"], cv["b"], y, cv["s"], cv["pad"], 0.2, 0, None)
+            be.conv2d_fwd(a, cv["W"], cv["b"], y, cv["s"], cv["pad"], 0.2, 0, None)
             acts.append(y)
             a = y
         flat = a.view(B, -1)
@@ -989,14 +936,10 @@ class F_net:
                 self._ready(f"features.{2 * li}.bias" if cv["gb"] is not None else f"features.{2 * li}.weight")
             if li > 0 or need_dx:
                 da = be.empty(*acts[li].shape)
-                pk = self._pcm_layer(li, acts[li].shape[2], acts[li].shape[3])
-                masked = False
-                if pk is not None:
-                    be.conv_pcm_dgrad(dz, pk[1], da, cv["W"].shape[2])
-                elif li > 0 and self._mask_fold:
+                masked = li > 0
+                if masked:
                     # the next step multiplies by the LeakyReLU mask of acts[li]: the same expression, in this launch's store
                     be.conv2d_dgrad(dz, cv["W"], da, cv["s"], cv["pad"], 0.0, mask=acts[li], mslope=0.2)
-                    masked = True
                 else:
                     be.conv2d_dgrad(dz, cv["W"], da, cv["s"], cv["pad"], 0.0)
             else:
@@ -1025,15 +968,7 @@ class F_net:
             self._leaf(lambda v=vzs[li], u=u, cv=cv: be.conv2d_wgrad(v, u, cv["gW"], cv["s"], cv["pad"], 1.0), vzs[li], u)
             self._ready_tail(f"features.{2 * li}.weight")            # this layer's range and everything behind it is final
             y = be.empty(*acts[li + 1].shape)
-            pk = self._pcm_layer(li, u.shape[2], u.shape[3])
-            if pk is not None:
-                be.conv_pcm_fwd(u, pk[0], None, y, cv["W"].shape[2], 1.0)
-                be.lrelu_bwd(y, acts[li + 1], y)
-            elif self._mask_fold:
-                be.conv2d_fwd(u, cv["W"], None, y, cv["s"], cv["pad"], 1.0, 0, None, mask=acts[li + 1], mslope=0.2)
-            else:
-                be.conv2d_fwd(u, cv["W"], None, y, cv["s"], cv["pad"], 1.0, 0, None)
-                be.lrelu_bwd(y, acts[li + 1], y)
+            be.conv2d_fwd(u, cv["W"], None, y, cv["s"], cv["pad"], 1.0, 0, None, mask=acts[li + 1], mslope=0.2)
             u = y
         uf = u.view(B, -1)
         self._leaf(lambda: be.linear_wgrad(v1, uf, g["fc.weight"], 1.0), v1, u)

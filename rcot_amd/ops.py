@@ -127,25 +127,21 @@ class HipBackend:
         self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
         self.ws = torch.empty(workspace_bytes // 4, dtype=torch.float32, device=self.device)
         self.ws_bytes = self.ws.numel() * 4
-        # weight-gradient overlap: leaf kernels of the backward sweep run on a second HIP stream (own split-K workspace)
-        # while the data-gradient chain continues; RCOT_OVERLAP=0 keeps everything on one stream
         # arithmetic of the big MFMA products (PREC_BY_NAME above).  RCOT_GEMM_PREC selects the process default (DEFAULT_PREC);
         # set ``backend.prec`` to switch at run time.
         self.prec = PREC_BY_NAME[os.environ.get("RCOT_GEMM_PREC", DEFAULT_PREC)]
         self._poison = os.environ.get("RCOT_POISON", "0") == "1"
+        # weight-gradient overlap: leaf kernels of the backward sweep run on a second HIP stream (own split-K workspace)
+        # while the data-gradient chain continues; RCOT_OVERLAP=0 keeps everything on one stream
         self.overlap = os.environ.get("RCOT_OVERLAP", "1") != "0"
-        self.attn_core = os.environ.get("RCOT_ATTN_CORE", "1") != "0"      # A/B switch: rcot_attn_core_fwd vs the four separate launches
-        self.attn_core_maxn = int(os.environ.get("RCOT_ATTN_CORE_MAXN", "4096"))   # largest plane rcot_attn_core_fwd is used on (it takes <= 65536; slower above 4096)
-        self.multi_launch = os.environ.get("RCOT_MULTI", "1") != "0"       # A/B switch: dV, dQ, dK of a block from one launch (rcot_gemm_kmajor_multi)
-        self.ln_fused = os.environ.get("RCOT_LN_FUSED", "1") != "0"        # A/B switch: LN statistics made by the projection kernel
-        self.pair_launch = os.environ.get("RCOT_PAIR", "1") != "0"         # A/B switch: data + weight gradient of a 1x1 from one launch
-        self.prod_stats = os.environ.get("RCOT_PROD_STATS", "1") != "0"     # A/B switch: LayerNorm statistics made by the epilogue of the product that stores the tensor (round 6)
-        self._raw_events = os.environ.get("RCOT_RAW_EVENTS", "1") != "0"   # A/B switch: hand-overs between the two streams on fence-free HIP events (_Handover)
+        self._raw_events = os.environ.get("RCOT_RAW_EVENTS", "1") != "0"   # hand-overs between the two streams on fence-free HIP events (_Handover)
+        self.attn_core_maxn = 4096         # largest plane rcot_attn_core_fwd is used on (it takes <= 65536; slower above 4096)
+        self.ln_fused = True               # LN statistics made by the projection kernel
+        self.prod_stats = True             # LayerNorm statistics made by the epilogue of the product that stores the tensor (round 6)
         self._ev_ring, self._ev_next = [], -1
         # networks built on this backend also keep the THREE-term weight packs of the bf16x6 arithmetic (1.5x the two-term packs,
-        # refreshed with them after every optimizer step): on when that arithmetic is the process default, or asked for
-        self._x6_nt = os.environ.get("RCOT_X6_NT", "1") != "0"
-        self.x6_packs = self.prec == _lib.PREC_BF16X6 or os.environ.get("RCOT_X6_PACKS", "0") == "1"
+        # refreshed with them after every optimizer step): on when that arithmetic is the process default
+        self.x6_packs = self.prec == _lib.PREC_BF16X6
         self._side = torch.cuda.Stream(device=self.device) if self.overlap else None
         self._ws_side = torch.empty_like(self.ws) if self.overlap else None
         # split-K slabs of weight gradients that wait for block_param_reduce(): their own arena (self.ws is reused by every
@@ -170,17 +166,10 @@ class HipBackend:
         self._gen = 0
         self._gen_event = [None, None]          # side-stream event after the reduce that read generation g
         self._held_gen = [[], []]               # tensors that reduce (and the side kernels before it) still read
-        # Side-stream policy, from full-iteration A/B runs under launch plans (round 4, B=8 128x128, ms per iteration):
-        #   deferred block closes (the parameter reduce of block i under block i+1): fp32 84.3 -> 83.6 WITHOUT, bf16x3 74.5 -> 74.3: off;
-        #   unpaired 1x1 weight gradients next to the data-gradient chain: fp32 83.6 with / 87.3 without (the fp32 products are
-        #   MFMA-bound and leave bandwidth to a neighbour), bf16x3 74.3 with / 73.3 without (both HBM-bound: the neighbour only
-        #   takes the bandwidth ln_bwd and the data gradient need): on for fp32 / bf16x6, off for bf16x3.
-        #   round 5 (profiles/r05_ab_sched.txt, two runs each): deferred closes fp32 77.21 / 77.31 -> 77.49 / 77.41 (still off), bf16x6
-        #   74.09 / 74.29 -> 73.85 / 73.71: on for bf16x6 (its weight gradients got shorter: the close no longer waits for the chain).
-        #   round 6 (fence-free hand-overs; profiles/r06_ab_sched_nofence.txt): deferred closes fp32 77.06 -> 78.04 (off), bf16x6
-        #   73.03 -> 72.48 (on), bf16x3 70.13 -> 70.71 (off); side-stream weight gradients now also pay in bf16x3 (71.9 -> 71.3).
+        # Side-stream policy: the launch that closes a block (its parameter reduce) runs on the side stream under the next block in
+        # bf16x6 only — fp32 77.06 -> 78.04 ms per iteration, bf16x6 73.03 -> 72.48, bf16x3 70.13 -> 70.71
+        # (profiles/r06_ab_sched_nofence.txt; the earlier rounds' runs are in NOTES.md)
         self._defer_close_env = os.environ.get("RCOT_DEFER_CLOSE")
-        self._side_wgrad_env = os.environ.get("RCOT_SIDE_WGRAD")
 
     # ------------------------------------------------------------------ leaf-kernel overlap
     @property
@@ -189,15 +178,6 @@ class HipBackend:
         if self._defer_close_env is not None:
             return self._defer_close_env != "0"
         return self.prec == _lib.PREC_BF16X6
-
-    @property
-    def side_wgrad(self):
-        """unpaired 1x1 weight gradients on the side stream (policy above); RCOT_SIDE_WGRAD=0/1 overrides"""
-        if self._side_wgrad_env is not None:
-            return self._side_wgrad_env != "0"
-        # round 6: on in every arithmetic.  With the hand-overs on fence-free events (_Handover) the two-term arithmetics gain too:
-        # bf16x3 71.9 (off) / 71.3 (on) ms per iteration in one call (profiles/r06_ab_sched_nofence.txt); rounds 4-5 had it off there
-        return True
 
     def side_run(self, fn, *hold):
         """Run ``fn`` (kernel launches that only READ ``hold`` tensors and WRITE parameter gradients) on the side
@@ -324,14 +304,6 @@ class HipBackend:
         c = lambda v, q: (v + q - 1) // q
         return (c(Ci, 16) * c(Co, 32) * 768,), (c(Co, 16) * c(Ci, 32) * 768,)
 
-    @property
-    def prec_nt(self):
-        """the arithmetic of the pixel-reduction products (weight gradients, Gram matrices): the backend's; RCOT_X6_NT=0 keeps
-        them exact fp32 under bf16x6 (the round-4 first form, for A/B runs)"""
-        if self.prec == _lib.PREC_BF16X6 and not self._x6_nt:
-            return _lib.PREC_FP32
-        return self.prec
-
     def pack_weight(self, W, WT, WP, fold=None, split=None, split6=None):
         """``fold`` = (ln_w, ln_b, WTf, c12): also write the LN-folded forward operand; ``split`` = (WTs, WPs, WTfs | None):
         also write the pre-split bf16 fragment packs of the bf16x3 producer / consumer kernel (rcot_pack_weight)."""
@@ -365,9 +337,8 @@ class HipBackend:
         want3 = prec is None or prec in _TWO_TERM
         want6 = prec is None or prec == _lib.PREC_BF16X6
         # the LN-folded operand WTf and its row constants serve the split arithmetics (LayerNorm applied in the epilogue); the exact-fp32
-        # kernel normalises the fragments in its loop and reads WT (round 6: a third of the repack's bytes for qkv / project_in less;
-        # RCOT_F32_PC=1, the opt-in exact product on the producer / consumer path, does read them)
-        want_fold = prec is None or prec != _lib.PREC_FP32 or os.environ.get("RCOT_F32_PC") == "1"
+        # kernel normalises the fragments in its loop and reads WT (round 6: a third of the repack's bytes for qkv / project_in less)
+        want_fold = prec is None or prec != _lib.PREC_FP32
         r16, r4 = (lambda v: (v + 15) // 16 * 16), (lambda v: (v + 3) // 4 * 4)
         for d, item in enumerate(items):
             W, WT, WP = item[:3]
@@ -478,7 +449,7 @@ class HipBackend:
         """Up to three independent plain products of gemm_kmajor from ONE launch (rcot_gemm_kmajor_multi): items =
         [(At, Bm, C, M, K, R | None, rowscale | None), ...] with the shapes gemm_kmajor takes and a common pixel count.  False (nothing
         launched) when the arithmetic in use runs these products on the split-bf16 kernel: the caller launches them one by one."""
-        if not self.multi_launch or self.prec in _TWO_TERM:
+        if self.prec in _TWO_TERM:
             return False
         arr = (_lib.KmajorDesc * len(items))()
         N = items[0][1].shape[3]
@@ -598,7 +569,7 @@ class HipBackend:
             mu, rs, lw, lb = ln
         _lib.check(self.L.rcot_conv1x1_wgrad(dY.data_ptr(), sdY, X.data_ptr(), sX, dW.data_ptr(), dW.stride(0), B, Ci,
                                              Co, N, _ptr(mu), _ptr(rs), _ptr(lw), _ptr(lb), beta, self.ws.data_ptr(),
-                                             self.ws_bytes, self.prec_nt, self._st()), "rcot_conv1x1_wgrad")
+                                             self.ws_bytes, self.prec, self._st()), "rcot_conv1x1_wgrad")
 
     def conv1x1_wgrad_slabs(self, dY, X, dW, ln: LN = None, region=(0, 1)):
         """The weight gradient of conv1x1_wgrad left as split-K slabs in part ``region`` = (index, count) of the slab arena; returns the descriptor block_param_reduce() takes (it adds the slabs to ``dW``), or None when the shape has
@@ -616,7 +587,7 @@ class HipBackend:
         ws = self._ws_slabs[idx * per:(idx + 1) * per]
         S, ld = C.c_int(0), C.c_int(0)
         rc = self.L.rcot_conv1x1_wgrad_slabs(dY.data_ptr(), sdY, X.data_ptr(), sX, B, Ci, Co, N, _ptr(mu), _ptr(rs), _ptr(lw),
-                                             _ptr(lb), ws.data_ptr(), per * 4, self.prec_nt, C.byref(S), C.byref(ld), self._st())
+                                             _ptr(lb), ws.data_ptr(), per * 4, self.prec, C.byref(S), C.byref(ld), self._st())
         if rc == _lib.EUNSUPPORTED:
             return None
         _lib.check(rc, "rcot_conv1x1_wgrad_slabs")
@@ -626,7 +597,7 @@ class HipBackend:
         """dX = W^T dY AND the weight gradient of the same dY left as split-K slabs (the descriptor of conv1x1_wgrad_slabs), from
         ONE launch (rcot_conv1x1_dgrad_wgrad_slabs, bf16x3 only).  None (nothing launched) when the shapes / the arithmetic have
         no paired kernel: the caller runs conv1x1_dgrad and conv1x1_wgrad_slabs / conv1x1_wgrad."""
-        if not self.pair_launch or self.prec != _lib.PREC_BF16X3 or packed is None or len(packed) < 4 or packed[3] is None:
+        if self.prec != _lib.PREC_BF16X3 or packed is None or len(packed) < 4 or packed[3] is None:
             return None
         Co, Ci = W.shape
         B, co, N, sdY = self._bcn(dY, "conv1x1_dgrad_wgrad dY")
@@ -683,7 +654,7 @@ class HipBackend:
         _lib.check(self.L.rcot_bmm_nt(A.data_ptr(), A.stride(2), A.stride(0), A.stride(1),
                                       Bm.data_ptr(), Bm.stride(2), Bm.stride(0), Bm.stride(1),
                                       C.data_ptr(), C.stride(2), C.stride(0), C.stride(1),
-                                      Zo, Zi, M, N, K, self.ws.data_ptr(), self.ws_bytes, self.prec_nt, self._st()), "rcot_bmm_nt")
+                                      Zo, Zi, M, N, K, self.ws.data_ptr(), self.ws_bytes, self.prec, self._st()), "rcot_bmm_nt")
 
     def bmm_nt_slabs(self, A, Bm):
         """bmm_nt left as split-K slabs in the workspace: (pointer, S, ld) for attn_softmax(), or None when the shape has no slab
@@ -693,7 +664,7 @@ class HipBackend:
         assert A.stride(3) == 1 and Bm.stride(3) == 1 and Bm.shape[3] == K
         S, ld = C.c_int(0), C.c_int(0)
         rc = self.L.rcot_bmm_nt_slabs(A.data_ptr(), A.stride(2), A.stride(0), A.stride(1), Bm.data_ptr(), Bm.stride(2),
-                                      Bm.stride(0), Bm.stride(1), Zo, Zi, M, N, K, self.ws.data_ptr(), self.ws_bytes, self.prec_nt,
+                                      Bm.stride(0), Bm.stride(1), Zo, Zi, M, N, K, self.ws.data_ptr(), self.ws_bytes, self.prec,
                                       C.byref(S), C.byref(ld), self._st())
         if rc == _lib.EUNSUPPORTED:
             return None
@@ -909,7 +880,7 @@ class HipBackend:
         _lib.check(self.L.rcot_conv_pcm_prep(dZ.data_ptr(), bz.data_ptr() + 4 * g["G"], ldb, B, Co, H, W, 0, self._st()), "rcot_conv_pcm_prep")
         _lib.check(self.L.rcot_conv_pcm_prep(X.data_ptr(), bx.data_ptr() + 4 * g["G"], ldb, B, Ci, H, W, 0, self._st()), "rcot_conv_pcm_prep")
         rc = self.L.rcot_conv_pcm_wgrad(bz.data_ptr() + 4 * g["G"], bx.data_ptr() + 4 * g["G"], ldb, g["N"], g["Wp"], Co, Ci, dW.data_ptr(),
-                                        beta, self.ws.data_ptr(), self.ws_bytes, self.prec_nt, self._st())
+                                        beta, self.ws.data_ptr(), self.ws_bytes, self.prec, self._st())
         if rc == _lib.EUNSUPPORTED:
             return False
         _lib.check(rc, "rcot_conv_pcm_wgrad")
@@ -1110,7 +1081,7 @@ class HipBackend:
         64x64 / 32x32 / 16x16 levels).  False when the shape has no such kernel: the caller runs the four separate launches."""
         B, heads, c, _ = Gn.shape
         N = u.shape[2] * u.shape[3]
-        if not self.attn_core or N > self.attn_core_maxn:
+        if N > self.attn_core_maxn:
             return False
         for t in (u, temp, sq, Gn, A, MfT):
             assert t.is_contiguous()
@@ -1145,7 +1116,7 @@ class HipBackend:
         """Everything attn_bwd_fused returns, in ONE launch (rcot_attn_core_bwd).  ``dM``: the dense [B, C, C] tensor or the slab
         descriptor (pointer, S <= 8, ld) of bmm_nt_slabs.  False when there is no such kernel for the head width."""
         B, heads, c, _ = A.shape
-        if not self.attn_core or c > 48:
+        if c > 48:
             # c = 96 (decoder_level1 / refinement / noise_level3): measured equal or slower than the two-launch form (57.8 vs 57 us
             # at the 128x128 level, 93 vs 84 us at 16x16): one workgroup per (head, image) walks 4x the MFMA work alone
             return False

@@ -1,4 +1,4 @@
-"""T_net forward at 2 x 256x256 with fixed weights: dump the output (RCOT_NT_OLD=1 selects the round-1 Gram kernel gate)."""
+"""T_net forward at 2 x 256x256 with fixed weights: dump the output (for comparing two builds, RCOT_LIB=)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "tests"))
