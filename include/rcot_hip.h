@@ -25,7 +25,7 @@ extern "C" {
 
 /* Bumped on EVERY signature change; returned by rcot_abi_version() (csrc/api.hip) and compared by the loader
  * (rcot_amd/lib.py ABI_VERSION, tests/test_abi.py) so that a stale prebuilt .so is refused, not mis-called. */
-#define RCOT_ABI_VERSION 25
+#define RCOT_ABI_VERSION 26
 
 /* Arithmetic of the MFMA products of the three GEMM-shaped entry points that take `prec` (rcot_gemm_kmajor,
  * rcot_conv1x1_wgrad, rcot_bmm_nt); operands and results are fp32 in memory either way.
@@ -360,7 +360,16 @@ int rcot_gp_penalty(const float* g, float* norms, float* u0, float* gp_out, int 
  * totals across ranks between rcot_ot_reduce and rcot_ot_grad for data parallelism). */
 int rcot_ot_reduce(const float* degraded, const float* restored, const float* target, float* sums, int B, long per,
                    void* stream);
-/* L1-spectrum branch (de_id >= 3): gF = d mean|FFT2(res)| / d res, spec[b] = sum |FFT2(res_b)|.  H, W powers of 2. */
+/* How the line FFT of rcot_ot_spectrum transforms a length n (host only: no launch, no stream).  Returns the number of stages and
+ * fills radices[0..stages) (product n; cap >= 10 always suffices): all 2 for a power of two (the in-place radix-2 kernel), else
+ * radix 4 as often as possible, then 2, then 3, 5, 7, 11, 13 (mixed-radix Stockham kernel).  Returns 0 when n has a prime factor
+ * above 13: Bluestein's algorithm over the power of two radices[0] = M, 2n - 1 <= M <= 2048.  RCOT_EINVAL for n < 2, a null
+ * pointer or cap too small; RCOT_EUNSUPPORTED for n > 1024.  rcot_ot_spectrum dispatches on this function's answer. */
+int rcot_fft_plan(int n, int* radices, int cap);
+/* L1-spectrum branch (de_id >= 3): gF = d mean|FFT2(res)| / d res, spec[b] = sum |FFT2(res_b)|.  H and W are any lengths in
+ * 2..1024, independently of each other (rows follow rcot_fft_plan(W), columns rcot_fft_plan(H)); RCOT_EUNSUPPORTED above 1024.
+ * ws: B*3*H*W complex values (8 bytes each), plus M more for each axis whose plan is Bluestein (its transformed chirp filter, made
+ * on the device by every call) — at most 32 KiB on top; RCOT_EWORKSPACE when ws_bytes is short. */
 int rcot_ot_spectrum(const float* degraded, const float* restored, const int* de_id, float* gF, float* spec, float* ws,
                      size_t ws_bytes, int B, int H, int W, void* stream);
 /* dout += d/d(restored) [ sigma*(rmse + sum_i f_i) + Sigma*mean|restored-target| ]; scal = {rmse, sum_i f_i (local),

@@ -1281,9 +1281,12 @@ class HipBackend:
     def ot_spectrum(self, degraded, restored, de_id, gF, spec):
         B, _, H, W = degraded.shape
         assert de_id.dtype == torch.int32 and de_id.is_cuda
-        _lib.check(self.L.rcot_ot_spectrum(degraded.data_ptr(), restored.data_ptr(), de_id.data_ptr(), gF.data_ptr(),
-                                           spec.data_ptr(), self.ws.data_ptr(), self.ws_bytes, B, H, W, self._st()),
-                   "rcot_ot_spectrum")
+        rc = self.L.rcot_ot_spectrum(degraded.data_ptr(), restored.data_ptr(), de_id.data_ptr(), gF.data_ptr(),
+                                     spec.data_ptr(), self.ws.data_ptr(), self.ws_bytes, B, H, W, self._st())
+        if rc == _lib.EUNSUPPORTED:
+            raise _lib.RcotKernelError(f"rcot_ot_spectrum: H = {H}, W = {W}: the line FFT of the L1-spectrum OT cost takes "
+                                       f"lengths up to 1024 per axis (rcot_fft_plan)")
+        _lib.check(rc, "rcot_ot_spectrum")
 
     def ot_grad(self, degraded, restored, target, de_id, gF, sums, spec, dout, scal, sigma, Sigma, global_batch):
         B = degraded.shape[0]

@@ -68,6 +68,18 @@ DE_IDS = {"denoise_15": 0, "denoise_25": 1, "denoise_50": 2, "derain": 3, "dehaz
           "lowlight": 6, "single": 7}   # util/dataset_utils.py:40
 
 
+def check_patch_size(P: int) -> int:
+    """The training patch sizes the networks take: a multiple of 32 with 32 <= P <= 1024.  F_net halves the patch with five
+    stride-2 convolutions (P/32 must be whole) and sizes its first fc layer as P*P/2 (Net_Restormer.py F_net: num_fea); the
+    line FFT of the OT cost (rcot_ot_spectrum) takes any length up to 1024.  Raises ValueError naming the reason."""
+    P = int(P)
+    if P < 32 or P > 1024 or P % 32:
+        raise ValueError(f"--patch_size {P}: the patch size must be a multiple of 32 with 32 <= P <= 1024 — F_net applies five "
+                         f"stride-2 convolutions (P/32 must be a whole number) and its fc layer is P*P/2 wide; the OT cost's "
+                         f"line FFT takes lengths up to 1024")
+    return P
+
+
 def freeze(model):      # utils.py:23-26
     """numerically inert on the explicit schedules (no autograd graph, no BN/dropout); on the autograd front end
     (rcot_amd.autograd.TNetModule / FNetModule) it is the reference's requires_grad_(False) + eval()"""
@@ -565,6 +577,10 @@ def main_mprnet():
 def main(argv=None):
     global opt
     opt = parser.parse_args(argv)
+    try:
+        check_patch_size(opt.patch_size)                   # before any network is built or the GPU is touched
+    except ValueError as e:
+        raise SystemExit(str(e))
     # --backbone mprnet: with a GPU the older transport map runs on the HIP kernels (rcot_amd/mprnet_hip.py) through everything below —
     # data folders, data parallelism, validation, launch plans; without one (or with RCOT_MPRNET_STOCK=1) the stock-ops loop
     hip_mprnet = opt.backbone == "mprnet" and torch.cuda.is_available() and os.environ.get("RCOT_MPRNET_STOCK", "0") != "1"
