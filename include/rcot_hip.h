@@ -25,7 +25,7 @@ extern "C" {
 
 /* Bumped on EVERY signature change; returned by rcot_abi_version() (csrc/api.hip) and compared by the loader
  * (rcot_amd/lib.py ABI_VERSION, tests/test_abi.py) so that a stale prebuilt .so is refused, not mis-called. */
-#define RCOT_ABI_VERSION 26
+#define RCOT_ABI_VERSION 27
 
 /* Arithmetic of the MFMA products of the three GEMM-shaped entry points that take `prec` (rcot_gemm_kmajor,
  * rcot_conv1x1_wgrad, rcot_bmm_nt); operands and results are fp32 in memory either way.
@@ -431,6 +431,32 @@ int rcot_bilinear_down2_bwd(const float* dy, float* dx, long planes, int H, int 
 int rcot_bilinear_up2(const float* x, const float* skip, float* y, long planes, int H, int W, void* stream);
 int rcot_bilinear_up2_bwd(const float* dy, float* dx, long planes, int H, int W, void* stream);
 int rcot_conv_weight_flip(const float* src, float* dst, const long long* table, int n, int Co, int Ci, int KH, int KW, void* stream);
+
+/* ---- whole-image validation at any size (csrc/imageio.hip; reference trainer.py:179-227, tester.py:56-113, evaluate.py:43-106) ------
+ * Geometry: the source is h x w, the padded image Hp x Wp (Hp >= h, Wp >= w), padding at the BOTTOM and RIGHT only.  `mode`: 0 none
+ * (Hp == h, Wp == w), 1 reflect as torch's 'reflect' (padded row r >= h reads row 2 (h - 1) - r, columns alike; needs Hp - h <= h - 1 and
+ * Wp - w <= w - 1), 2 replicate (row h - 1 / column w - 1).  A geometry the mode cannot pad returns RCOT_EINVAL and launches nothing.
+ *  rcot_image_ingest : img uint8 [h][w][3] (HWC, device) -> out float [3][Hp][Wp] = (float)u8 / 255.0f (correctly rounded), padded: the
+ *                      bits of F.pad(img.permute(2,0,1).float().div(255)[None], (0, Wp-w, 0, Hp-h), mode).
+ *  rcot_pad2d        : src float [planes][h][w] -> dst [planes][Hp][Wp], same modes, the bits of F.pad.
+ *  rcot_image_egress : restored float [3][Hp][Wp]; degraded (optional) the same geometry; target (optional) uint8 [h][w][3].  Outputs, each
+ *                      optional (at least one):
+ *                        out_u8 [h][w][3] : the crop of `restored` quantised as torchvision's save_image does for one image — clamp(0,1),
+ *                                           * 255, + 0.5, clamp(0,255), truncate, each step rounded to fp32 (no contraction);
+ *                        res_u8 [h][w][3] : the same chain on (degraded - restored) * res_scale (two fp32 roundings); needs `degraded`;
+ *                        stats double[4]  : needs `target` and ws.  [0] sum over 3 h w of ((double)restored - (double)((float)t / 255.0f))^2
+ *                                           (unclamped: under the PSNR of trainer.py:225); [1] sum (out_u8 - t)^2, exact (64-bit integers:
+ *                                           under skimage's PSNR of uint8 images, evaluate.py:84); [2] the sum of evaluate.py's SSIM map
+ *                                           (:43-63, the 2 x 2 box window, cropped [5:-5]) over the three channels between target and out_u8,
+ *                                           window moments in integers, the quotient in fp64; [3] its element count
+ *                                           3 max(0, h - 10) max(0, w - 10).
+ *                      The sums are bitwise reproducible: per-workgroup partials in ws (24 bytes per workgroup of 4 rows x 256 columns, ws
+ *                      8-byte aligned; too small: RCOT_EWORKSPACE), then one fixed-order pass in a second launch.  No atomics. */
+int rcot_image_ingest(const unsigned char* img, int h, int w, float* out, int Hp, int Wp, int mode, void* stream);
+int rcot_pad2d(const float* src, float* dst, long planes, int h, int w, int Hp, int Wp, int mode, void* stream);
+int rcot_image_egress(const float* restored, const float* degraded, const unsigned char* target, int h, int w, int Hp, int Wp,
+                      float res_scale, unsigned char* out_u8, unsigned char* res_u8, double* stats, float* ws, size_t ws_bytes,
+                      void* stream);
 
 #ifdef __cplusplus
 }

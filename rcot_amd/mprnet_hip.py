@@ -129,6 +129,8 @@ class MPRNetHip:
     ``backward(dout)`` (accumulates parameter gradients), ``zero_grad``, ``state_dict`` / ``load_state_dict`` with the reference's 127
     names (the shared PReLU slope is listed 22 times there, stored once here), ``grad_ready_hook`` for the bucketed all-reduce."""
 
+    size_multiple = 4        # H and W of an input must be multiples of this (two x0.5 resamplings); rcot_amd/wholeimage.py pads to it
+
     def __init__(self, backend=None, seed: Optional[int] = None):
         if backend is None:
             from .ops import default_backend

@@ -511,6 +511,8 @@ class T_net:
     """Two-pass Restormer transport map.  Same constructor signature / defaults as the reference
     (Net_Restormer.py:216-227); only the reference's default architecture is implemented."""
 
+    size_multiple = 8        # H and W of an input must be multiples of this (three PixelUnshuffle(2) stages); rcot_amd/wholeimage.py pads to it
+
     def __init__(self, inp_channels=3, out_channels=3, dim=48, num_blocks=(4, 6, 6, 8), num_refinement_blocks=4,
                  heads=(1, 2, 4, 8), ffn_expansion_factor=2.66, bias=False, LayerNorm_type="WithBias",
                  decoder=False, backend=None, seed: Optional[int] = None):

@@ -1307,6 +1307,76 @@ class HipBackend:
                                           int(seed) & 0xFFFFFFFFFFFFFFFF, deg_out.data_ptr(), clean_out.data_ptr(), self._st()),
                    "rcot_patch_prep")
 
+    # ------------------------------------------------------------------ whole-image validation at any size (csrc/imageio.hip)
+    PAD_MODES = {None: 0, "none": 0, "reflect": 1, "replicate": 2}
+
+    def _u8_image(self, t, what: str, h: Optional[int] = None, w: Optional[int] = None):
+        if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous() or t.dim() != 3 or t.shape[2] != 3:
+            raise _lib.RcotKernelError(f"{what}: expected a contiguous uint8 [h, w, 3] image on the HIP device")
+        if h is not None and tuple(t.shape[:2]) != (h, w):
+            raise _lib.RcotKernelError(f"{what}: expected {h} x {w} pixels, got {t.shape[0]} x {t.shape[1]}")
+
+    def _dense_planes(self, t, what: str):
+        self._chk(t, what)
+        if t.dim() < 2 or not t.is_contiguous():
+            raise _lib.RcotKernelError(f"{what}: planes must be dense [..., H, W]")
+
+    def image_ingest(self, img, Hp: int, Wp: int, mode, out=None):
+        """img uint8 [h, w, 3] on the device -> float [1, 3, Hp, Wp] = img / 255 in CHW, padded bottom / right by ``mode``
+        ("none" | "reflect" | "replicate"): the bits of F.pad(img.permute(2, 0, 1).float().div(255)[None], ...) (rcot_image_ingest)"""
+        self._u8_image(img, "image_ingest")
+        h, w, _ = img.shape
+        if out is None:
+            out = self.empty(1, 3, Hp, Wp)
+        self._dense_planes(out, "image_ingest")
+        if out.numel() != 3 * Hp * Wp:
+            raise _lib.RcotKernelError("image_ingest: out must hold [3, Hp, Wp] floats")
+        _lib.check(self.L.rcot_image_ingest(img.data_ptr(), h, w, out.data_ptr(), Hp, Wp, self.PAD_MODES[mode], self._st()),
+                   "rcot_image_ingest")
+        return out
+
+    def pad2d(self, x, Hp: int, Wp: int, mode, out=None):
+        """x float [..., h, w] (dense) -> [..., Hp, Wp], padded bottom / right by ``mode``: the bits of F.pad (rcot_pad2d)"""
+        self._dense_planes(x, "pad2d")
+        h, w = x.shape[-2:]
+        planes = x.numel() // (h * w) if h * w else 0
+        if out is None:
+            out = self.empty(*x.shape[:-2], Hp, Wp)
+        self._dense_planes(out, "pad2d")
+        if tuple(out.shape) != (*x.shape[:-2], Hp, Wp):
+            raise _lib.RcotKernelError("pad2d: out must be [..., Hp, Wp] with the leading dimensions of x")
+        _lib.check(self.L.rcot_pad2d(x.data_ptr(), out.data_ptr(), planes, h, w, Hp, Wp, self.PAD_MODES[mode], self._st()), "rcot_pad2d")
+        return out
+
+    def image_egress(self, restored, h: int, w: int, degraded=None, target=None, res_scale: float = 2.0, want_out: bool = True,
+                     want_res: bool = False, want_stats: bool = False, ws=None):
+        """restored float [(1,) 3, Hp, Wp] -> (out_u8, res_u8, stats): the h x w crop quantised to uint8 [h, w, 3] as ``trainer.save_image``
+        does, the same for (degraded - restored) * res_scale, and the float64 [4] statistics against ``target`` (uint8 [h, w, 3]) that
+        ``wholeimage.image_metrics`` turns into PSNR / SSIM.  Whatever is not asked for is None.  One launch, two with statistics
+        (per-workgroup partials in ``ws``, default the backend's workspace, then a fixed-order sum): rcot_image_egress."""
+        self._dense_planes(restored, "image_egress")
+        if restored.numel() != 3 * restored.shape[-2] * restored.shape[-1]:
+            raise _lib.RcotKernelError("image_egress: restored must be one image, [3, Hp, Wp]")
+        Hp, Wp = restored.shape[-2:]
+        if want_res:
+            if degraded is None:
+                raise _lib.RcotKernelError("image_egress: the residual needs the degraded image")
+            self._dense_planes(degraded, "image_egress")
+            if degraded.numel() != restored.numel() or tuple(degraded.shape[-2:]) != (Hp, Wp):
+                raise _lib.RcotKernelError("image_egress: degraded and restored differ in shape")
+        if want_stats:
+            if target is None:
+                raise _lib.RcotKernelError("image_egress: the statistics need the target image")
+            self._u8_image(target, "image_egress", h, w)
+        ws = self.ws if ws is None else ws
+        out_u8 = torch.empty(h, w, 3, dtype=torch.uint8, device=self.device) if want_out else None
+        res_u8 = torch.empty(h, w, 3, dtype=torch.uint8, device=self.device) if want_res else None
+        stats = torch.empty(4, dtype=torch.float64, device=self.device) if want_stats else None
+        _lib.check(self.L.rcot_image_egress(restored.data_ptr(), _ptr(degraded if want_res else None), _ptr(target if want_stats else None),
+                                            h, w, Hp, Wp, float(res_scale), _ptr(out_u8), _ptr(res_u8), _ptr(stats), ws.data_ptr(),
+                                            ws.numel() * ws.element_size(), self._st()), "rcot_image_egress")
+        return out_u8, res_u8, stats
+
     # ------------------------------------------------------------------ optimizers
     def rmsprop_step(self, p, g, sq, n, lr, alpha=0.99, eps=1e-8, grad_scale=1.0):
         _lib.check(self.L.rcot_rmsprop_step(p.data_ptr(), g.data_ptr(), sq.data_ptr(), n, lr, alpha, eps, grad_scale,

@@ -15,6 +15,11 @@ PSNR / SSIM over the two folders as ``evaluate.calculate_evaluation_floder`` com
 not in this image, so both metrics are restated in numpy from their definitions: PSNR = skimage's for uint8 images, SSIM = the
 script's own 2 x 2 box-window form).  FID (tester.py:115-118) needs a pretrained Inception network and is not computed.
 
+Superset: ``--pad reflect|replicate`` restores the WHOLE image at any size: it is padded at the bottom and right to the network's size
+multiple on the device, restored and cropped back (rcot_amd/wholeimage.py); neither crop above is applied, and a pair is skipped only for
+a shape mismatch or when reflect cannot pad it.  ``--metrics device`` takes the three PNGs and both metrics from the egress kernel
+(rcot_image_egress: same 8-bit values, same sums) instead of writing the folders and reading them back.
+
 Superset: ``--tile T`` processes the image as overlapping T x T tiles (``--overlap`` pixels, averaged where tiles overlap) for sizes
 one does not want to hold whole; the default is the reference's whole-image call.  Restormer takes H, W multiples of 8 (its three
 PixelUnshuffle stages; the reference raises on other sizes), MPRNet multiples of 4.
@@ -42,6 +47,12 @@ parser.add_argument("--noise_sigma", type=float, default=None, help="tester_nois
 parser.add_argument("--seed", type=int, default=0, help="seed of the added noise")
 parser.add_argument("--tile", type=int, default=0, help="superset: tile size (0 = whole image, the reference's behaviour)")
 parser.add_argument("--overlap", type=int, default=32, help="superset: tile overlap in pixels")
+parser.add_argument("--pad", choices=["none", "reflect", "replicate"], default="none",
+                    help="superset: pad bottom / right to the network's size multiple, restore the whole image, crop back (none = the "
+                         "reference's crops and skips)")
+parser.add_argument("--metrics", choices=["folders", "device"], default="folders",
+                    help="superset: folders = PSNR / SSIM read back from the written PNGs (the reference's way); device = PNGs and metrics "
+                         "from the egress kernel's 8-bit outputs and sums")
 
 
 # ------------------------------------------------------------------------------- metrics (evaluate.py)
@@ -107,9 +118,13 @@ def load_network(path: str):
     return tn, 8
 
 
-def restore(net, x: torch.Tensor, tile: int = 0, overlap: int = 32, mult: int = 8) -> torch.Tensor:
-    """``net(x)`` whole (tile 0), or as overlapping tiles averaged where they overlap"""
+def restore(net, x: torch.Tensor, tile: int = 0, overlap: int = 32, mult: int = 8, pad=None) -> torch.Tensor:
+    """``net(x)`` whole (tile 0), or as overlapping tiles averaged where they overlap.  ``pad`` ("reflect" | "replicate"): any H, W —
+    padded to multiples of ``mult`` first, cropped back after (rcot_amd/wholeimage.py)"""
     _, _, H, W = x.shape
+    if pad not in (None, "none"):
+        from .wholeimage import restore_any_size
+        return restore_any_size(net, x, mult, pad, tile, overlap).out[:, :, :H, :W].contiguous()
     if not tile or (tile >= H and tile >= W):
         return net(x)
     tile = max(mult, tile // mult * mult)
@@ -125,6 +140,69 @@ def restore(net, x: torch.Tensor, tile: int = 0, overlap: int = 32, mult: int = 
     return acc / cnt
 
 
+def _report(psnr, ssim, pmax, smax, pmin, smin, done):
+    print("FID value: not computed (needs a pretrained Inception network; tester.py:115-118)")
+    print("PSNR: Averyge {:.5f},   best {:.5f},   worst {:.5f}".format(psnr, pmax, pmin))
+    print("SSIM: Averyge {:.5f},   best {:.5f},   worst {:.5f}".format(ssim, smax, smin))
+    return dict(images=done, psnr=psnr, ssim=ssim, psnr_best=pmax, psnr_worst=pmin, ssim_best=smax, ssim_worst=smin)
+
+
+def _main_any_size(opt, net):
+    """``--pad`` other than none and / or ``--metrics device``: ingest (or pad2d for the noisy float input), the network on the padded
+    image, and the egress kernel for the crop, the three 8-bit images and the statistics.  The size multiple is the network's own."""
+    from PIL import Image
+    from .wholeimage import image_metrics, pad_geometry, restore_any_size
+    be, mult = net.be, net.size_multiple
+    padded = opt.pad != "none"
+    device_metrics = opt.metrics == "device"
+    deg_list, tar_list = sorted(glob.glob(opt.degset + "*")), sorted(glob.glob(opt.tarset + "*"))
+    rng = np.random.default_rng(opt.seed)
+    noisy = opt.noise_sigma is not None
+    sizes, stats = [], []
+    for deg_name, tar_name in zip(deg_list, tar_list):
+        name = os.path.basename(tar_name)
+        print("Processing ", deg_name)
+        deg, tar = np.array(Image.open(deg_name).convert("RGB")), np.array(Image.open(tar_name).convert("RGB"))
+        if deg.shape != tar.shape:
+            print(f"  skipped: degraded {deg.shape[0]} x {deg.shape[1]} and target {tar.shape[0]} x {tar.shape[1]} differ")
+            continue
+        h, w = deg.shape[:2]
+        if not padded:                                                # the reference's crops (tester.py:77-84, tester_noise.py:84-86)
+            if noisy:
+                if (h % 4) or (w % 4):
+                    deg, tar = deg[1:h, 1:w], tar[1:h, 1:w]
+            else:
+                deg, tar = deg[:h - h % 4, :w - w % 4], tar[:h - h % 4, :w - w % 4]
+            h, w = deg.shape[:2]
+        try:
+            pad_geometry(h, w, mult, opt.pad)
+        except ValueError as e:
+            print(f"  skipped: {e}")
+            continue
+        tar_d = torch.from_numpy(np.ascontiguousarray(tar)).to(be.device)
+        if noisy:                                                     # the noise is drawn on the host (numpy's generator, as the reference)
+            x = torch.from_numpy(np.ascontiguousarray(deg.transpose(2, 0, 1))).float().div(255).unsqueeze(0)
+            x = x + torch.from_numpy(rng.normal(size=tar.transpose(2, 0, 1).shape) * opt.noise_sigma / 255.0).float()
+        else:
+            x = torch.from_numpy(np.ascontiguousarray(deg))
+        r = restore_any_size(net, x, mult, opt.pad, opt.tile, opt.overlap)
+        out_u8, res_u8, st = be.image_egress(r.out, h, w, degraded=r.x, target=tar_d, res_scale=3.0 if noisy else 2.0, want_out=True,
+                                             want_res=True, want_stats=device_metrics)
+        Image.fromarray(res_u8.cpu().numpy()).save(os.path.join(opt.saveres, name))
+        Image.fromarray(out_u8.cpu().numpy()).save(os.path.join(opt.save, name))
+        Image.fromarray(np.ascontiguousarray(tar)).save(os.path.join(opt.savetar, name))
+        sizes.append((h, w))
+        stats.append(st)
+    if not device_metrics:
+        return _report(*evaluate_folders(opt.savetar, opt.save), len(sizes))
+    if not sizes:
+        nan = float("nan")
+        return _report(nan, nan, nan, nan, nan, nan, 0)
+    m = [image_metrics(s, h, w) for s, (h, w) in zip(torch.stack(stats).cpu().tolist(), sizes)]      # four numbers per image, read once
+    ps, ss = [v["psnr_u8"] for v in m], [v["ssim"] for v in m]
+    return _report(sum(ps) / len(ps), sum(ss) / len(ss), max(ps), max(ss), min(ps), min(ss), len(sizes))
+
+
 def main(argv=None):
     from PIL import Image
     from .trainer import save_image
@@ -134,6 +212,8 @@ def main(argv=None):
     for d in (opt.save, opt.savetar, opt.saveres):
         os.makedirs(d, exist_ok=True)
     net, mult = load_network(opt.model)
+    if opt.pad != "none" or opt.metrics == "device":
+        return _main_any_size(opt, net)
     deg_list, tar_list = sorted(glob.glob(opt.degset + "*")), sorted(glob.glob(opt.tarset + "*"))
     rng = np.random.default_rng(opt.seed)
     noisy = opt.noise_sigma is not None
@@ -166,11 +246,7 @@ def main(argv=None):
         save_image(out.cpu(), os.path.join(opt.save, name))
         save_image(gt, os.path.join(opt.savetar, name))
         done += 1
-    print("FID value: not computed (needs a pretrained Inception network; tester.py:115-118)")
-    psnr, ssim, pmax, smax, pmin, smin = evaluate_folders(opt.savetar, opt.save)
-    print("PSNR: Averyge {:.5f},   best {:.5f},   worst {:.5f}".format(psnr, pmax, pmin))
-    print("SSIM: Averyge {:.5f},   best {:.5f},   worst {:.5f}".format(ssim, smax, smin))
-    return dict(images=done, psnr=psnr, ssim=ssim)
+    return _report(*evaluate_folders(opt.savetar, opt.save), done)
 
 
 if __name__ == "__main__":

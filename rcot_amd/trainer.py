@@ -59,6 +59,9 @@ parser.add_argument("--backbone", choices=["restormer", "mprnet"], default="rest
                     help="restormer: Net_Restormer.T_net on the HIP kernels (the hot path).  mprnet: the reference's older Net.T_net "
                          "(BASELINE configs[0]) — on the HIP kernels when a GPU is visible (rcot_amd/mprnet_hip.py), else on stock "
                          "PyTorch ops with torch autograd on the CPU (rcot_amd/mprnet.py; RCOT_MPRNET_STOCK=1 forces that form)")
+parser.add_argument("--val_pad", choices=["none", "reflect", "replicate"], default="none",
+                    help="validation at any image size: pad bottom / right to the network's size multiple on the device, restore, crop "
+                         "(rcot_amd/wholeimage.py); none = the reference's rule, images that are not multiples of 8 are skipped")
 parser.add_argument("--synthetic", action="store_true", help="seeded synthetic patches (no dataset folders needed)")
 parser.add_argument("--iters", type=int, default=20, help="iterations per epoch with --synthetic")
 
@@ -450,8 +453,43 @@ def psnr(pred, gt, data_range: float = 1.0) -> float:
     return float("inf") if err == 0.0 else 10.0 * math.log10(data_range * data_range / err)
 
 
-def evaluate(Tnet, deg_list, tar_list):
+def _evaluate_padded(Tnet, deg_list, tar_list, pad):
+    """evaluate() with ``pad``: every pair of equal shapes that ``pad`` can bring to the network's size multiple goes through
+    rcot_image_ingest, the network and rcot_image_egress; one squared-error sum per image is read back, after the walk."""
+    import numpy as np
+    from PIL import Image
+    from .wholeimage import image_metrics, pad_geometry, restore_any_size
+    be, mult = Tnet.be, Tnet.size_multiple
+    sizes, sums = [], []
+    for deg_name, tar_name in zip(deg_list, tar_list):
+        deg_img = np.array(Image.open(deg_name).convert('RGB'))
+        tar_img = np.array(Image.open(tar_name).convert('RGB'))
+        if deg_img.shape != tar_img.shape:
+            continue
+        h, w = deg_img.shape[:2]
+        try:
+            pad_geometry(h, w, mult, pad)
+        except ValueError as e:
+            if par.rank() == 0:
+                print(f"validation: {deg_name} skipped: {e}")
+            continue
+        r = restore_any_size(Tnet, torch.from_numpy(np.ascontiguousarray(deg_img)), mult, pad)
+        tar = torch.from_numpy(np.ascontiguousarray(tar_img)).to(be.device)
+        sums.append(be.image_egress(r.out, h, w, target=tar, want_out=False, want_stats=True)[2])
+        sizes.append((h, w))
+    pp = 0.0
+    if sums:
+        for s, (h, w) in zip(torch.stack(sums).cpu().tolist(), sizes):
+            pp += image_metrics(s, h, w)["psnr_float"]
+    return pp / len(deg_list) if len(deg_list) else float("nan")
+
+
+def evaluate(Tnet, deg_list, tar_list, pad=None):
     """Whole-image inference + PSNR over the validation folders — reference trainer.py:179-227.
+
+    ``pad`` ("reflect" | "replicate"; ``--val_pad``): images of any size are padded to the network's size multiple on the device,
+    restored and cropped, so only shape mismatches (and sizes reflect cannot pad) are left out; the divisor stays ``len(deg_list)``.
+    Without it:
 
     Same walk and the same skip rules (:195-198: H or W not a multiple of 4, or shape mismatch, are skipped but still
     counted in the divisor :226), plus two guards the reference lacks: sizes that are multiples of 4 but not of 8 are
@@ -463,6 +501,8 @@ def evaluate(Tnet, deg_list, tar_list):
     pp = 0.0
     if par.rank() == 0:
         print('----------validating-----------')
+    if pad not in (None, "none"):
+        return _evaluate_padded(Tnet, deg_list, tar_list, pad)
     dev = Tnet.be.device
     for deg_name, tar_name in zip(deg_list, tar_list):
         deg_img = np.array(Image.open(deg_name).convert('RGB'))
@@ -666,7 +706,7 @@ def main(argv=None):
         if rank == 0:
             dt = time.time() - t0
             print(f"epoch {epoch}: {len(loader) * opt.batchSize / dt:.1f} patches/s")
-            p = evaluate(Tnet, deg_list, tar_list)                         # :149
+            p = evaluate(Tnet, deg_list, tar_list, pad=opt.val_pad)        # :149
             os.makedirs("./checksample/" + str(opt.type), exist_ok=True)
             with open("./checksample/" + str(opt.type) + "/validation_results.txt", "a") as f:      # :151-153
                 f.write(f"Patchsize {opt.patch_size} Epoch {epoch}, psnr {p:.4f}, Batchsize {opt.batchSize}\n")
