@@ -25,7 +25,7 @@ extern "C" {
 
 /* Bumped on EVERY signature change; returned by rcot_abi_version() (csrc/api.hip) and compared by the loader
  * (rcot_amd/lib.py ABI_VERSION, tests/test_abi.py) so that a stale prebuilt .so is refused, not mis-called. */
-#define RCOT_ABI_VERSION 27
+#define RCOT_ABI_VERSION 28
 
 /* Arithmetic of the MFMA products of the three GEMM-shaped entry points that take `prec` (rcot_gemm_kmajor,
  * rcot_conv1x1_wgrad, rcot_bmm_nt); operands and results are fp32 in memory either way.
@@ -457,6 +457,35 @@ int rcot_pad2d(const float* src, float* dst, long planes, int h, int w, int Hp, 
 int rcot_image_egress(const float* restored, const float* degraded, const unsigned char* target, int h, int w, int Hp, int Wp,
                       float res_scale, unsigned char* out_u8, unsigned char* res_u8, double* stats, float* ws, size_t ws_bytes,
                       void* stream);
+
+/* ---- standard image-quality figures (csrc/quality.hip; rcot_amd/quality.py, the testers' --ssim_window / --color) --------------------
+ * The two published SSIM protocols and PSNR, in RGB or on the Y channel, between two uint8 [h][w][3] (HWC, device) images a and b — the
+ * 8-bit values that land in the PNGs, data range 255.  (The reference's own evaluate.py:53-73 is the 2 x 2 box window that
+ * rcot_image_egress sums; val_utils.py:50-66 calls skimage's default, `uniform7` below.)
+ *   space   0 rgb : the three channels are three planes.
+ *           1 y   : one plane, the 8-bit luma of ITU-R BT.601 as MATLAB's rgb2ycbcr / basicsr's bgr2ycbcr(y_only) give it for uint8
+ *                   input, defined in integers so that it has one answer:  n = 65481 R + 128553 G + 24966 B,
+ *                   Y = 16 + (n + 127500) / 255000 (integer division: round-half-up; 16..235).
+ *   window  0 uniform7 : 7 taps of 1/7 per axis, cov_norm = 49/48 (skimage's defaults, use_sample_covariance=True).
+ *           1 gauss11  : 11 taps exp(-x^2 / (2 1.5^2)), x = -5..5, normalised to sum 1, cov_norm = 1 (cv2.getGaussianKernel(11, 1.5),
+ *                        basicsr's calculate_ssim, skimage with gaussian_weights=True, use_sample_covariance=False).  The taps are
+ *                        computed on the host in fp64 and passed to the kernel by value.
+ *   The window is applied separably to a, b, a^2, b^2, ab, giving ux, uy, uxx, uyy, uxy;  vx = cov_norm (uxx - ux^2), vy and vxy alike;
+ *   C1 = (0.01 255)^2, C2 = (0.03 255)^2;  S = ((2 ux uy + C1)(2 vxy + C2)) / ((ux^2 + uy^2 + C1)(vx + vy + C2)).
+ *   S is evaluated only where the whole window lies inside the image, (h - win + 1)(w - win + 1) positions per plane (skimage's crop by
+ *   (win - 1) / 2, basicsr's [5:-5]: no border rule is involved); the metric is the mean of S over all positions of all planes.
+ *   PSNR = 10 log10(255^2 / mean((a - b)^2)) over the planes of the space.
+ *  rcot_image_quality : stats double[4] (8-byte aligned):
+ *                        [0] sum (a - b)^2 over the planes, exact (64-bit integers);  [1] its element count, planes h w;
+ *                        [2] sum S (uniform7: window moments in integers, exact; gauss11: fp64; the quotient and the sum in fp64);
+ *                        [3] the position count, planes max(0, h - win + 1) max(0, w - win + 1) — 0, with [2] = 0, when h < win or w < win.
+ *                       RCOT_EINVAL for null pointers, h or w < 1, an unknown window or space (and beyond the kernel's reach: w > 2^24,
+ *                       h > 16 * 65535); nothing is launched.  The sums are bitwise
+ *                       reproducible: per-workgroup partials in ws, then one fixed-order pass in a second launch, no atomics.  ws needs
+ *                       16 * planes * ceil(h / 16) * ceil(w / 32) bytes (planes = 3 for rgb, 1 for y), 8-byte aligned; smaller or
+ *                       misaligned: RCOT_EWORKSPACE, nothing is launched and stats is untouched. */
+int rcot_image_quality(const unsigned char* a, const unsigned char* b, int h, int w, int window, int space, double* stats, float* ws,
+                       size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1377,6 +1377,36 @@ class HipBackend:
                                             ws.numel() * ws.element_size(), self._st()), "rcot_image_egress")
         return out_u8, res_u8, stats
 
+    # ------------------------------------------------------------------ standard image-quality figures (csrc/quality.hip)
+    WINDOWS = {"uniform7": 0, "gauss11": 1}
+    SPACES = {"rgb": 0, "y": 1}
+    QUALITY_TILE = (16, 32)                        # TH x TW of csrc/quality.hip: map positions of one workgroup
+
+    @classmethod
+    def image_quality_ws_bytes(cls, h: int, w: int, space: str) -> int:
+        """workspace bytes rcot_image_quality needs (include/rcot_hip.h): 16 per workgroup, one workgroup per tile and plane"""
+        th, tw = cls.QUALITY_TILE
+        return 16 * (3 if space == "rgb" else 1) * (-(-h // th)) * (-(-w // tw))
+
+    def image_quality(self, a_u8, b_u8, window: str, space: str, ws=None):
+        """a_u8, b_u8 uint8 [h, w, 3] on the device -> float64 [4]: the exact squared-error sum over the planes of ``space`` ("rgb" | "y")
+        and its element count, the sum of the SSIM map of ``window`` ("uniform7" | "gauss11") and its position count — what
+        ``quality.quality_metrics`` turns into PSNR / SSIM.  Two launches (per-workgroup partials in ``ws``, default the backend's
+        workspace, then a fixed-order sum): rcot_image_quality."""
+        self._u8_image(a_u8, "image_quality")
+        h, w, _ = a_u8.shape
+        self._u8_image(b_u8, "image_quality", h, w)
+        if window not in self.WINDOWS:
+            raise _lib.RcotKernelError(f"image_quality: invalid argument: window {window!r}, expected one of {tuple(self.WINDOWS)}")
+        if space not in self.SPACES:
+            raise _lib.RcotKernelError(f"image_quality: invalid argument: color space {space!r}, expected one of {tuple(self.SPACES)}")
+        ws = self.ws if ws is None else ws
+        stats = torch.empty(4, dtype=torch.float64, device=self.device)
+        _lib.check(self.L.rcot_image_quality(a_u8.data_ptr(), b_u8.data_ptr(), h, w, self.WINDOWS[window], self.SPACES[space],
+                                             stats.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(), self._st()),
+                   "rcot_image_quality")
+        return stats
+
     # ------------------------------------------------------------------ optimizers
     def rmsprop_step(self, p, g, sq, n, lr, alpha=0.99, eps=1e-8, grad_scale=1.0):
         _lib.check(self.L.rcot_rmsprop_step(p.data_ptr(), g.data_ptr(), sq.data_ptr(), n, lr, alpha, eps, grad_scale,

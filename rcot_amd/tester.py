@@ -23,6 +23,13 @@ a shape mismatch or when reflect cannot pad it.  ``--metrics device`` takes the 
 Superset: ``--tile T`` processes the image as overlapping T x T tiles (``--overlap`` pixels, averaged where tiles overlap) for sizes
 one does not want to hold whole; the default is the reference's whole-image call.  Restormer takes H, W multiples of 8 (its three
 PixelUnshuffle stages; the reference raises on other sizes), MPRNet multiples of 4.
+
+Superset: ``--ssim_window uniform7|gauss11`` and ``--color y`` report the figures of published tables instead of the reference's own
+(rcot_amd/quality.py): uniform7 = skimage's default structural_similarity (the AirNet / PromptIR protocol, the reference's
+util/val_utils.py:50-66), gauss11 = the 11 x 11, sigma 1.5 Gaussian window (basicsr, MATLAB-style scripts), y = PSNR and SSIM on the
+BT.601 luma (deraining tables).  ``--metrics folders`` computes them on the host from the PNGs read back, ``--metrics device`` with
+rcot_image_quality on the 8-bit images already on the device.  A line naming the protocol is printed before the report.  The defaults
+(box2, rgb) print what the reference prints.
 """
 from __future__ import annotations
 
@@ -53,6 +60,11 @@ parser.add_argument("--pad", choices=["none", "reflect", "replicate"], default="
 parser.add_argument("--metrics", choices=["folders", "device"], default="folders",
                     help="superset: folders = PSNR / SSIM read back from the written PNGs (the reference's way); device = PNGs and metrics "
                          "from the egress kernel's 8-bit outputs and sums")
+parser.add_argument("--ssim_window", choices=["box2", "uniform7", "gauss11"], default="box2",
+                    help="superset: box2 = the reference's 2 x 2 window (evaluate.py); uniform7 = skimage's default SSIM (AirNet / PromptIR "
+                         "tables); gauss11 = the 11 x 11, sigma 1.5 Gaussian window (basicsr / MATLAB-style)")
+parser.add_argument("--color", choices=["rgb", "y"], default="rgb",
+                    help="superset: y = PSNR / SSIM on the BT.601 luma of YCbCr (deraining tables) instead of the three RGB planes")
 
 
 # ------------------------------------------------------------------------------- metrics (evaluate.py)
@@ -85,16 +97,27 @@ def ssim_image(im1: np.ndarray, im2: np.ndarray) -> float:
     return float(np.mean([ssim_plane(im1[:, :, c], im2[:, :, c]) for c in range(im1.shape[2])]))
 
 
-def evaluate_folders(path1: str, path2: str):
-    """evaluate.calculate_evaluation_floder (:65-106): mean / best / worst PSNR and SSIM over the sorted file pairs"""
+def _standard(opt) -> bool:
+    """a protocol other than the reference's own was asked for"""
+    return opt.ssim_window != "box2" or opt.color != "rgb"
+
+
+def evaluate_folders(path1: str, path2: str, ssim_window: str = "box2", color: str = "rgb"):
+    """evaluate.calculate_evaluation_floder (:65-106): mean / best / worst PSNR and SSIM over the sorted file pairs; with another
+    ``ssim_window`` / ``color`` the protocols of rcot_amd/quality.py"""
     from PIL import Image
+    if (ssim_window, color) == ("box2", "rgb"):
+        psnr, ssim = psnr_uint8, ssim_image
+    else:
+        from . import quality as Q
+        psnr, ssim = (lambda x, y: Q.psnr_u8(x, y, color)), (lambda x, y: Q.ssim_windowed(x, y, ssim_window, color))
     a, b = sorted(os.listdir(path1)), sorted(os.listdir(path2))
     ps, ss = [], []
     for n1, n2 in zip(a, b):
         i1 = np.array(Image.open(os.path.join(path1, n1)).convert("RGB"))
         i2 = np.array(Image.open(os.path.join(path2, n2)).convert("RGB"))
-        ps.append(psnr_uint8(i1, i2))
-        ss.append(ssim_image(i1, i2))
+        ps.append(psnr(i1, i2))
+        ss.append(ssim(i1, i2))
     if not ps:
         nan = float("nan")
         return nan, nan, nan, nan, nan, nan
@@ -140,11 +163,14 @@ def restore(net, x: torch.Tensor, tile: int = 0, overlap: int = 32, mult: int = 
     return acc / cnt
 
 
-def _report(psnr, ssim, pmax, smax, pmin, smin, done):
+def _report(psnr, ssim, pmax, smax, pmin, smin, done, ssim_window="box2", color="rgb"):
+    if (ssim_window, color) != ("box2", "rgb"):
+        print(f"metrics: ssim {ssim_window}, color {color}")
     print("FID value: not computed (needs a pretrained Inception network; tester.py:115-118)")
     print("PSNR: Averyge {:.5f},   best {:.5f},   worst {:.5f}".format(psnr, pmax, pmin))
     print("SSIM: Averyge {:.5f},   best {:.5f},   worst {:.5f}".format(ssim, smax, smin))
-    return dict(images=done, psnr=psnr, ssim=ssim, psnr_best=pmax, psnr_worst=pmin, ssim_best=smax, ssim_worst=smin)
+    return dict(images=done, psnr=psnr, ssim=ssim, psnr_best=pmax, psnr_worst=pmin, ssim_best=smax, ssim_worst=smin,
+                ssim_window=ssim_window, color=color)
 
 
 def _main_any_size(opt, net):
@@ -155,6 +181,8 @@ def _main_any_size(opt, net):
     be, mult = net.be, net.size_multiple
     padded = opt.pad != "none"
     device_metrics = opt.metrics == "device"
+    standard = _standard(opt)                                         # rcot_image_quality instead of the egress kernel's own sums
+    proto = (opt.ssim_window, opt.color)
     deg_list, tar_list = sorted(glob.glob(opt.degset + "*")), sorted(glob.glob(opt.tarset + "*"))
     rng = np.random.default_rng(opt.seed)
     noisy = opt.noise_sigma is not None
@@ -187,26 +215,37 @@ def _main_any_size(opt, net):
             x = torch.from_numpy(np.ascontiguousarray(deg))
         r = restore_any_size(net, x, mult, opt.pad, opt.tile, opt.overlap)
         out_u8, res_u8, st = be.image_egress(r.out, h, w, degraded=r.x, target=tar_d, res_scale=3.0 if noisy else 2.0, want_out=True,
-                                             want_res=True, want_stats=device_metrics)
+                                             want_res=True, want_stats=device_metrics and not standard)
+        if device_metrics and standard:
+            st = be.image_quality(tar_d, out_u8, opt.ssim_window, opt.color)
         Image.fromarray(res_u8.cpu().numpy()).save(os.path.join(opt.saveres, name))
         Image.fromarray(out_u8.cpu().numpy()).save(os.path.join(opt.save, name))
         Image.fromarray(np.ascontiguousarray(tar)).save(os.path.join(opt.savetar, name))
         sizes.append((h, w))
         stats.append(st)
     if not device_metrics:
-        return _report(*evaluate_folders(opt.savetar, opt.save), len(sizes))
+        return _report(*evaluate_folders(opt.savetar, opt.save, *proto), len(sizes), *proto)
     if not sizes:
         nan = float("nan")
-        return _report(nan, nan, nan, nan, nan, nan, 0)
-    m = [image_metrics(s, h, w) for s, (h, w) in zip(torch.stack(stats).cpu().tolist(), sizes)]      # four numbers per image, read once
-    ps, ss = [v["psnr_u8"] for v in m], [v["ssim"] for v in m]
-    return _report(sum(ps) / len(ps), sum(ss) / len(ss), max(ps), max(ss), min(ps), min(ss), len(sizes))
+        return _report(nan, nan, nan, nan, nan, nan, 0, *proto)
+    host = torch.stack(stats).cpu().tolist()                          # four numbers per image, read once
+    if standard:
+        from .quality import quality_metrics
+        m = [quality_metrics(s) for s in host]
+        ps, ss = [v["psnr"] for v in m], [v["ssim"] for v in m]
+    else:
+        m = [image_metrics(s, h, w) for s, (h, w) in zip(host, sizes)]
+        ps, ss = [v["psnr_u8"] for v in m], [v["ssim"] for v in m]
+    return _report(sum(ps) / len(ps), sum(ss) / len(ss), max(ps), max(ss), min(ps), min(ss), len(sizes), *proto)
 
 
 def main(argv=None):
     from PIL import Image
     from .trainer import save_image
     opt = parser.parse_args(argv)
+    if opt.ssim_window == "box2" and opt.color == "y" and opt.metrics == "device":
+        raise SystemExit("--ssim_window box2 with --color y (the reference's 2 x 2 map on the luma plane) is computed on the host only: "
+                         "use --metrics folders, or --ssim_window uniform7 | gauss11")
     if not torch.cuda.is_available():
         raise SystemExit("No GPU found: rcot_amd.tester runs the HIP path only")
     for d in (opt.save, opt.savetar, opt.saveres):
@@ -246,7 +285,7 @@ def main(argv=None):
         save_image(out.cpu(), os.path.join(opt.save, name))
         save_image(gt, os.path.join(opt.savetar, name))
         done += 1
-    return _report(*evaluate_folders(opt.savetar, opt.save), done)
+    return _report(*evaluate_folders(opt.savetar, opt.save, opt.ssim_window, opt.color), done, opt.ssim_window, opt.color)
 
 
 if __name__ == "__main__":
