@@ -12,14 +12,12 @@
 //   * otherwise the partial Gram blocks / sums go to the workspace and softmax_fold_kernel — one workgroup per (head, image,
 //     slice of output columns) — adds them in a fixed order, then softmax + fold (also MFMA fp32).
 #include <cstdlib>
-#include "common.h"
+#include "gemm_core.h"
 #include "../../include/rcot_hip.h"
 
 using namespace rcot;
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float clamp_norm(float sumsq) { return fmaxf(sqrtf(sumsq), 1e-12f); }
 

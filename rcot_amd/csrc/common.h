@@ -65,6 +65,40 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
     return t;
 }
 
+// Fixed-order totals of per-workgroup partials, for ONE workgroup of 256 threads: ND streams of nb fp64 values (stream d at
+// part_d[d * nb ..)) and one stream of nb int64 values.  Strided per-thread sums (the loads of eight steps in flight, the sums in
+// order), then a tree over the 256 threads; every thread returns with the totals.
+template <int ND>
+__device__ __forceinline__ void final_sums(const double* __restrict__ part_d, const long long* __restrict__ part_i, long nb,
+                                           double (&tot_d)[ND], long long& tot_i) {
+    __shared__ double sd[ND][256];
+    __shared__ long long si[256];
+    const int t = threadIdx.x;
+    double s[ND] = {};
+    long long n = 0;
+#pragma unroll 8
+    for (long b = t; b < nb; b += 256) {
+#pragma unroll
+        for (int d = 0; d < ND; ++d) s[d] += part_d[d * nb + b];
+        n += part_i[b];
+    }
+#pragma unroll
+    for (int d = 0; d < ND; ++d) sd[d][t] = s[d];
+    si[t] = n;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) {
+#pragma unroll
+            for (int d = 0; d < ND; ++d) sd[d][t] += sd[d][t + o];
+            si[t] += si[t + o];
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int d = 0; d < ND; ++d) tot_d[d] = sd[d][0];
+    tot_i = si[0];
+}
+
 // Unsigned division by a runtime-invariant divisor (host precomputes magic/shift).
 struct FastDiv {
     uint32_t d, magic, shift;
@@ -111,6 +145,20 @@ __device__ __forceinline__ void gelu_and_grad(float a, float& g, float& dg) {
 }
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// "not one of my shapes": what a dispatcher inside the library (dispatch.h) answers so that its caller tries the next kernel
+// family.  Never returned by an entry point.
+constexpr int NOT_ELIGIBLE = -100;
+
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// workgroups of bs threads that cover n elements, between 1 and cap (grid-stride kernels)
+inline int grid_for(long n, int bs = 256, int cap = 8192) {
+    long g = (n + bs - 1) / bs;
+    if (g > cap) g = cap;
+    if (g < 1) g = 1;
+    return (int)g;
+}
 
 // Name of the kernel symbol the calling thread's last dispatcher chose (printf-style; api.hip).  bench.py reads it back through
 // rcot_last_kernel() to attribute the time of an entry point to the kernel family that ran (several families serve one entry point).

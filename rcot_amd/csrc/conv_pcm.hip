@@ -13,25 +13,13 @@
 //                        then dX(2y + i - 1, 2x + j - 1) = dQ_ij(y, x)  (merge kernel).
 // Every shifted operand row is CONTIGUOUS in n, so a reduction slab is 16 channel rows at a per-tap offset: exactly what the LDS-DMA
 // producer streams (sources need only 4-byte alignment).  Outputs at padding positions are computed and dropped (colmap = -1).
-#include "common.h"
+#include "gemm_core.h"
+#include "dispatch.h"
 #include "../../include/rcot_hip.h"
-
-namespace rcot {
-int conv_pcm_x3w(const void* Apk, int M, int K, const float* Xp, long ldb, int N, const int* tapoff, int ntaps, const float* bias,
-                 float lrelu, const int* colmap, float* Y, long ldy, float* ws, size_t ws_bytes, hipStream_t st);
-}
 
 using namespace rcot;
 
 namespace {
-
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {
-    const f32x2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
 
 // mode 0: out[c][b][yp][xp] = X[b][c][yp - 1][xp - 4]                        geometry (H + 2) x (W + 8)
 // mode 1: out[(ij, c)][b][yp][xp] = X[b][c][2 (yp - 1) + i - 1][2 (xp - 4) + j - 1]   geometry (H/2 + 2) x (W/2 + 8)

@@ -4,7 +4,7 @@
 //   penalty and the generator step) and patch-embed 48 -> 3.
 // As implicit GEMMs these have M = 3 and fill 3 of 64 tile rows (2-3 TFLOP/s); here they are plain FMA kernels
 // bound by reading the wide operand once.
-#include "common.h"
+#include "dispatch.h"
 #include "../../include/rcot_hip.h"
 
 namespace rcot {
@@ -221,15 +221,15 @@ __global__ __launch_bounds__(256) void wgrad_few_out_kernel(const float* __restr
 
 }  // namespace
 
-// ---- dispatch helpers used by conv_ops.hip; return -100 when the shape is not one of the thin cases -----------
+// ---- dispatch helpers used by conv_ops.hip; return NOT_ELIGIBLE when the shape is not one of the thin cases -----------
 int try_conv_few_out(const float* in, const float* wt, long wb, long sco, long sci, long sky, long skx, const float* bias,
                      const float* R, float* out, int B, int Cin, int H, int W, int Cout, int KS, int pad, float lrelu,
                      float beta, hipStream_t st) {
-    if (Cout != 3 || (KS != 3 && KS != 5) || 2 * pad != KS - 1 || (W & 3) || B > 65535) return -100;
-    if ((reinterpret_cast<uintptr_t>(out) & 15) || (R && (reinterpret_cast<uintptr_t>(R) & 15))) return -100;
+    if (Cout != 3 || (KS != 3 && KS != 5) || 2 * pad != KS - 1 || (W & 3) || B > 65535) return NOT_ELIGIBLE;
+    if ((reinterpret_cast<uintptr_t>(out) & 15) || (R && (reinterpret_cast<uintptr_t>(R) & 15))) return NOT_ELIGIBLE;
     const dim3 grid(cdiv(W, TILE_W), cdiv(H, TILE_H), B);
     const size_t smem = sizeof(float) * 4 * (size_t)Cin * KS * KS;
-    if (smem > 96 * 1024) return -100;
+    if (smem > 96 * 1024) return NOT_ELIGIBLE;
     if (KS == 3)
         RCOT_LAUNCH((conv_few_out_kernel<3, 3>), grid, dim3(256), smem, st, in, wt, wb, sco, sci, sky, skx, bias, R, out, Cin, H,
                            W, pad, lrelu, beta);
@@ -242,8 +242,8 @@ int try_conv_few_out(const float* in, const float* wt, long wb, long sco, long s
 
 int try_wgrad_few_out(const float* dy, const float* x, float* dw, int B, int Cin, int H, int W, int Cout, int KS, int pad,
                       float beta, hipStream_t st) {
-    if (Cout != 3 || KS != 3 || pad != 1 || beta != 1.0f || (W & 3) || (H & 3)) return -100;
-    if ((reinterpret_cast<uintptr_t>(dy) & 15) || (reinterpret_cast<uintptr_t>(x) & 15)) return -100;
+    if (Cout != 3 || KS != 3 || pad != 1 || beta != 1.0f || (W & 3) || (H & 3)) return NOT_ELIGIBLE;
+    if ((reinterpret_cast<uintptr_t>(dy) & 15) || (reinterpret_cast<uintptr_t>(x) & 15)) return NOT_ELIGIBLE;
     constexpr int RS = 16;
     const int tpp = cdiv(H, RS) * (W >> 2);
     const long nt = (long)B * Cin * tpp;
@@ -252,7 +252,7 @@ int try_wgrad_few_out(const float* dy, const float* x, float* dw, int B, int Cin
     if (tpp % 256 == 0) { RCOT_WF(256, 64); }
     else if (tpp % 64 == 0) { RCOT_WF(64, 64); }
     else if (tpp < 64 && (tpp & (tpp - 1)) == 0) { RCOT_WF(1, tpp); }
-    else return -100;
+    else return NOT_ELIGIBLE;
 #undef RCOT_WF
     RCOT_LAUNCH_CHECK();
     return RCOT_OK;

@@ -17,6 +17,18 @@
 namespace rcot {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+
+__device__ __forceinline__ unsigned pk_bf16(float a, float b) {                      // v_cvt_pk_bf16_f32 (rne): a -> low half
+    const f32x2 v = {a, b};
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
+}
 
 constexpr int BK = 16;
 constexpr int LDS_PAD = 4;
@@ -812,19 +824,17 @@ static __global__ __launch_bounds__(256) void splitk_reduce_few4_kernel(GemmDims
 }
 // the cases splitk_reduce_few4_kernel takes
 inline bool reduce4_ok(const GemmDims& d, const EpiP& e, int Z) {
-    auto a16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    if ((d.N & 3) || e.R || e.transC || e.cmap || (e.ldc & 3) || (e.sCo & 3) || (e.sCi & 3) || !a16(e.C) || !a16(d.ws)) return false;
+    if ((d.N & 3) || e.R || e.transC || e.cmap || (e.ldc & 3) || (e.sCo & 3) || (e.sCi & 3) || !al16(e.C) || !al16(d.ws)) return false;
     if (e.fold && (e.foldP.d & 3)) return false;
-    if (e.mask && !a16(e.mask)) return false;
+    if (e.mask && !al16(e.mask)) return false;
     return (long)d.M * d.N * Z < (1L << 31);
 }
 
 // ------------------------------------------------------------------ host-side launch
 // float4 epilogue is legal when every row start of C (and R) is 16-byte aligned
 inline bool epi_vec_ok(const EpiP& e, int N) {
-    auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    if ((N & 3) || (e.ldc & 3) || (e.sCo & 3) || (e.sCi & 3) || !a16(e.C) || e.transC || e.cmap || e.fold) return false;
-    if (e.R && ((e.ldr & 3) || (e.sRo & 3) || (e.sRi & 3) || !a16(e.R))) return false;
+    if ((N & 3) || (e.ldc & 3) || (e.sCo & 3) || (e.sCi & 3) || !al16(e.C) || e.transC || e.cmap || e.fold) return false;
+    if (e.R && ((e.ldr & 3) || (e.sRo & 3) || (e.sRi & 3) || !al16(e.R))) return false;
     return true;
 }
 

@@ -18,6 +18,7 @@
 //   Columns m >= M of At may hold anything (rows of C are independent; they are never stored).
 #include <cstdlib>
 #include "gemm_core.h"
+#include "dispatch.h"
 #include "../../include/rcot_hip.h"
 
 using namespace rcot;
@@ -65,8 +66,6 @@ struct XXP {
     float* st_mu; float* st_rs; long sST;
     EpiP ep;
 };
-
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // epilogue_vec (gemm_core.h) for a tile that holds EVERY row (channel) of its pixels (one row tile: M <= BM, 1 x 4 wavefronts: each
 // wavefront all rows of 32 pixels), plus the per-pixel WithBias-LayerNorm statistics of the values it stores (Net_Restormer.py:186-189:
@@ -666,8 +665,6 @@ int launch_xx(XXP p, bool ln, int Z, hipStream_t st) {
     return RCOT_OK;
 }
 
-inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 inline EpiP p_ep_probe(float* C, long ldc, long sCo, long sCi, const float* R, long ldr, long sRo, long sRi) {
     EpiP e{};
     e.C = C; e.ldc = ldc; e.sCo = sCo; e.sCi = sCi; e.R = R; e.ldr = ldr; e.sRo = sRo; e.sRi = sRi;
@@ -675,16 +672,6 @@ inline EpiP p_ep_probe(float* C, long ldc, long sCo, long sCi, const float* R, l
 }
 
 }  // namespace
-
-namespace rcot {
-int try_gemm_kmajor_x3(const float* At, long lda, long sAo, long sAi, const float* Bm, long ldb, long sBo, long sBi,
-                       const EpiP& ep, const float* ln_mu, const float* ln_rs, long sLN, const float* ln_c1,
-                       const float* ln_c2, int Zo, int Zi, int M, int N, int K, float* ws, size_t ws_bytes, hipStream_t st);
-int try_gemm_kmajor_x3w(const float* At, long lda, long sAo, long sAi, const void* Apk, const float* Bm, long ldb, long sBo,
-                        long sBi, const EpiP& ep, const float* ln_mu, const float* ln_rs, long sLN, const float* ln_c1,
-                        const float* ln_c2, int Zo, int Zi, int M, int N, int K, float* ws, size_t ws_bytes, hipStream_t st,
-                        bool ln_compute, int nterms);
-}
 
 extern "C" {
 
@@ -737,7 +724,7 @@ int rcot_gemm_kmajor(const float* At, long lda, long sAo, long sAi, int a_rows, 
         const int rcw = try_gemm_kmajor_x3w(AtF, lda, sAo, sAi, Asplit, Bm, ldb, sBo, sBi, p.ep, ln_mu, ln_rs, sLN, ln_c12,
                                             ln_c12 + ((M + 3) & ~3), Zo, Zi, M, N, K, ws, ws_bytes, (hipStream_t)stream, true,
                                             prec == RCOT_PREC_BF16X6 ? 3 : 2);
-        return rcw == -100 ? RCOT_EUNSUPPORTED : rcw;
+        return rcw == NOT_ELIGIBLE ? RCOT_EUNSUPPORTED : rcw;
     }
     if (prec == RCOT_PREC_BF16X6 && Asplit && (!ln || (AtF && ln_c12))) {
         // fp32-class arithmetic on the bf16 pipe: three-term split, six products — the producer / consumer kernel with the THREE-term
@@ -747,7 +734,7 @@ int rcot_gemm_kmajor(const float* At, long lda, long sAo, long sAi, int a_rows, 
         const int rcw = try_gemm_kmajor_x3w(ln ? AtF : At, lda, sAo, sAi, Asplit, Bm, ldb, sBo, sBi, p.ep, ln_mu, ln_rs, sLN,
                                             ln ? ln_c12 : nullptr, ln ? ln_c12 + ((M + 3) & ~3) : nullptr, Zo, Zi, M, N, K, ws, ws_bytes,
                                             (hipStream_t)stream, false, 3);
-        if (rcw != -100) return rcw;
+        if (rcw != NOT_ELIGIBLE) return rcw;
     }
     if (prec == RCOT_PREC_BF16X3 && (!ln || (AtF && ln_c12))) {
         // with a LayerNorm prologue the split kernel multiplies the LN-FOLDED operand and applies mu/rstd in its epilogue
@@ -757,12 +744,12 @@ int rcot_gemm_kmajor(const float* At, long lda, long sAo, long sAi, int a_rows, 
             const int rcw = try_gemm_kmajor_x3w(ln ? AtF : At, lda, sAo, sAi, Asplit, Bm, ldb, sBo, sBi, p.ep, ln_mu, ln_rs, sLN, c1,
                                                 ln ? ln_c12 + ((M + 3) & ~3) : nullptr, Zo, Zi, M, N, K, ws, ws_bytes,
                                                 (hipStream_t)stream, false, 2);
-            if (rcw != -100) return rcw;
+            if (rcw != NOT_ELIGIBLE) return rcw;
         }
         const int rc = try_gemm_kmajor_x3(ln ? AtF : At, lda, sAo, sAi, Bm, ldb, sBo, sBi, p.ep, ln_mu, ln_rs, sLN, c1,
                                           ln ? ln_c12 + ((M + 3) & ~3) : nullptr, Zo, Zi, M, N, K, ws, ws_bytes,
                                           (hipStream_t)stream);
-        if (rc != -100) return rc;
+        if (rc != NOT_ELIGIBLE) return rc;
     }
     const long pad96 = (long)cdiv(M, 96) * 96, pad128 = (long)cdiv(M, 128) * 128;
     const long big_tiles = (long)cdiv(M, 128) * (N / 128) * Z;

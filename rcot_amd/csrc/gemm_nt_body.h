@@ -34,7 +34,6 @@ struct NTP {
     int one;                                  // X3 kernels: the single product hi * hi (RCOT_PREC_BF16X1)
 };
 
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 // wait until at most y slabs (NPW vm operations each) of this wave are outstanding, 0 <= y <= 3
 template <int NPW> __device__ __forceinline__ void wait_slabs(int y) {
     if (y <= 0) wait_vm<0>();
@@ -47,7 +46,6 @@ template <int N> __device__ __forceinline__ void wait_lgkm() { asm volatile("s_w
 // Fragment reads are issued as inline asm: the compiler then neither places an "LDS-DMA may alias" s_waitcnt vmcnt(0)
 // in front of them (which would serialise the DMA ring) nor sinks each read next to its consumer.  The value of a
 // read may only be used after the matching wait_lgkm<>() + pin(): pin() is the data-dependence fence.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 lds_read64(uint32_t byte_addr) {
     f32x2 v;
     asm volatile("ds_read_b64 %0, %1" : "=v"(v) : "v"(byte_addr));
@@ -55,9 +53,6 @@ __device__ __forceinline__ f32x2 lds_read64(uint32_t byte_addr) {
 }
 __device__ __forceinline__ void pin(f32x2& v) { asm volatile("" : "+v"(v)); }
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x4 lds_read128(uint32_t byte_addr) {
     f32x4 v;
     asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(byte_addr));
@@ -527,7 +522,7 @@ __device__ __forceinline__ void nt_body(const NTP& p, const int bx, const int bz
 }  // namespace rcot_nt
 
 namespace rcot {
-// (gemm_nt_glds.hip) parameter block, tile shape and split factor of one pixel-reduction product; -100: not eligible
+// (gemm_nt_glds.hip) parameter block, tile shape and split factor of one pixel-reduction product, or NOT_ELIGIBLE
 int nt_configure(int M, int N, int K, int Zo, int Zi, const float* A, long lda, long sAo, long sAi, const float* B, long ldb,
                  long sBo, long sBi, int Kb, long sAk, long sBk, const float* mu, const float* rs, long sLNb, const float* lnw,
                  const float* lnb, float* ws, size_t ws_bytes, int prec, int conv_wp, rcot_nt::NTP* out, int* out_cfg, int slots = 640);

@@ -14,6 +14,7 @@
 // per wave) and the affine normalisation is applied to the B fragment in registers.
 #include <cstdlib>
 #include "gemm_core.h"
+#include "dispatch.h"
 #include "../../include/rcot_hip.h"
 
 using namespace rcot;
@@ -129,19 +130,18 @@ namespace rcot {
 static int g_nt_coop_override = -1;      // rcot_debug_nt_coop(): -1 = the environment's RCOT_NT_COOP (read once), else the mask to use
 
 // Parameter block, tile shape (cfg 0..5: 128x128, 128x96, 96x128, 128x64, 64x128, 64x64) and split factor of one product.
-// Returns RCOT_OK, or -100 when the product is not eligible for this kernel family.  Used by try_gemm_nt_glds below and by the
+// Returns RCOT_OK, or NOT_ELIGIBLE when the product is not eligible for this kernel family.  Used by try_gemm_nt_glds below and by the
 // paired data-gradient + weight-gradient launch of gemm_x3w.hip.
 int nt_configure(int M, int N, int K, int Zo, int Zi, const float* A, long lda, long sAo, long sAi, const float* B, long ldb,
                  long sBo, long sBi, int Kb, long sAk, long sBk, const float* mu, const float* rs, long sLNb, const float* lnw,
                  const float* lnb, float* ws, size_t ws_bytes, int prec, int conv_wp, rcot_nt::NTP* out, int* out_cfg, int slots) {
     using namespace rcot_nt;
-    auto a16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     const int Z = Zo * Zi;
     if (!ws || (K & 15) || (lda & 3) || (ldb & 3) || (sAo & 3) || (sAi & 3) || (sBo & 3) || (sBi & 3) || (sAk & 3) ||
-        (sBk & 3) || !a16(A) || !a16(B) || (Kb && (Kb & 15)) || Z > 16384)
-        return -100;
-    if (mu && ((sLNb & 3) || !a16(mu) || !a16(rs))) return -100;
-    if (M < 33 || N < 33) return -100;                 // 64- or 128-row DMA images: tiny channel counts stay on the 64x64 engine
+        (sBk & 3) || !al16(A) || !al16(B) || (Kb && (Kb & 15)) || Z > 16384)
+        return NOT_ELIGIBLE;
+    if (mu && ((sLNb & 3) || !al16(mu) || !al16(rs))) return NOT_ELIGIBLE;
+    if (M < 33 || N < 33) return NOT_ELIGIBLE;                 // 64- or 128-row DMA images: tiny channel counts stay on the 64x64 engine
     NTP p{};
     p.M = M; p.N = N; p.K = K; p.Zi = Zi;
     p.A = A; p.lda = lda; p.sAo = sAo; p.sAi = sAi;
@@ -179,7 +179,7 @@ int nt_configure(int M, int N, int K, int Zo, int Zi, const float* A, long lda, 
     }
     const size_t per = (size_t)M * p.ldws * Z * sizeof(float);
     while (S > 1 && per * S > ws_bytes) --S;
-    if (per * S > ws_bytes) return -100;
+    if (per * S > ws_bytes) return NOT_ELIGIBLE;
     if ((long)Z * S > 65535) S = 65535 / Z;
     p.kchunk = cdiv(cdiv(nslab, (int)S), 1) * BK;
     p.S = cdiv(K, p.kchunk);
@@ -191,7 +191,7 @@ int nt_configure(int M, int N, int K, int Zo, int Zi, const float* A, long lda, 
     return RCOT_OK;
 }
 
-// Returns RCOT_OK after launching, or a negative "not eligible" code (-100) so that the caller can use the general engine.
+// Returns RCOT_OK after launching, or NOT_ELIGIBLE so that the caller can use the general engine.
 int try_gemm_nt_glds(int M, int N, int K, int Zo, int Zi, const float* A, long lda, long sAo, long sAi, const float* B,
                      long ldb, long sBo, long sBi, int Kb, long sAk, long sBk, const float* mu, const float* rs,
                      long sLNb, const float* lnw, const float* lnb, const EpiP& ep, float* ws, size_t ws_bytes,

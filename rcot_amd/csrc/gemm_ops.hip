@@ -3,21 +3,10 @@
 // batched small-matrix products of MDTA (Gram over H*W, attention apply, their gradients)
 // and the critic's Linear layers.  See include/rcot_hip.h for the contract.
 #include "gemm_core.h"
+#include "dispatch.h"
 #include "../../include/rcot_hip.h"
 
 using namespace rcot;
-
-namespace rcot {
-// LDS-DMA pipelined pixel-reduction kernel (gemm_nt_glds.hip); returns -100 when the problem is not eligible.
-int pair_dgrad_wgrad_x3(const float* WP, long ldp, const void* WPs, const float* dY, long sdYb, float* dX, long sdXb, const float* X,
-                        long sXb, int B, int Ci, int Co, int N, const float* ln_mu, const float* ln_rs, const float* ln_w,
-                        const float* ln_b, float* ws, size_t ws_bytes, float* ws_slabs, size_t ws_slabs_bytes, int* S_out,
-                        int* ld_out, hipStream_t st);
-int try_gemm_nt_glds(int M, int N, int K, int Zo, int Zi, const float* A, long lda, long sAo, long sAi, const float* B,
-                     long ldb, long sBo, long sBi, int Kb, long sAk, long sBk, const float* mu, const float* rs,
-                     long sLNb, const float* lnw, const float* lnb, const EpiP& ep, float* ws, size_t ws_bytes,
-                     hipStream_t st, int prec, int* slabs_S = nullptr, int* slabs_ld = nullptr, int conv_wp = 0);
-}
 
 namespace {
 
@@ -31,8 +20,6 @@ template <class Cfg> using BStrK = StridedLoader<Cfg::BN, Cfg::SB, true>;
 template <class Cfg> using BXc = XContigLoader<Cfg::BN, Cfg::SB>;
 template <class Cfg> using AKc = KContigLoader<Cfg::BM, Cfg::SA>;
 template <class Cfg> using BKc = KContigLoader<Cfg::BN, Cfg::SB>;
-
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 EpiP epi_default(float* C, long ldc) {
     EpiP e{};
@@ -135,7 +122,7 @@ int rcot_conv1x1_wgrad(const float* dY, long sdYb, const float* X, long sXb, flo
     ep.beta = beta;
     const int rc = try_gemm_nt_glds(Co, Ci, d.K, 1, 1, dY, N, 0, 0, X, N, 0, 0, N, sdYb, sXb, ln_mu, ln_rs, N, ln_w, ln_b, ep,
                                     ws, ws_bytes, (hipStream_t)stream, prec);
-    if (rc != -100) return rc;
+    if (rc != NOT_ELIGIBLE) return rc;
     return run_kcontig(d, ap, bp, ep, 1, ws, ws_bytes, (hipStream_t)stream);
 }
 
@@ -147,7 +134,7 @@ int rcot_conv_pcm_wgrad(const float* dZp, const float* Xp, long ld, int N, int W
     ep.beta = beta;
     const int rc = try_gemm_nt_glds(Co, 9 * Ci, N, 1, 1, dZp, ld, 0, 0, Xp, ld, 0, 0, 0, 0, 0, nullptr, nullptr, 0, nullptr, nullptr, ep, ws,
                                     ws_bytes, (hipStream_t)stream, prec, nullptr, nullptr, Wp);
-    return rc == -100 ? RCOT_EUNSUPPORTED : rc;
+    return rc == NOT_ELIGIBLE ? RCOT_EUNSUPPORTED : rc;
 }
 
 int rcot_conv1x1_wgrad_slabs(const float* dY, long sdYb, const float* X, long sXb, int B, int Ci, int Co, int N,
@@ -159,7 +146,7 @@ int rcot_conv1x1_wgrad_slabs(const float* dY, long sdYb, const float* X, long sX
     EpiP ep{};
     const int rc = try_gemm_nt_glds(Co, Ci, B * N, 1, 1, dY, N, 0, 0, X, N, 0, 0, N, sdYb, sXb, ln_mu, ln_rs, N, ln_w, ln_b, ep, ws,
                                     ws_bytes, (hipStream_t)stream, prec, S, ldws);
-    return rc == -100 ? RCOT_EUNSUPPORTED : rc;
+    return rc == NOT_ELIGIBLE ? RCOT_EUNSUPPORTED : rc;
 }
 
 int rcot_conv1x1_dgrad_wgrad_slabs(const float* WP, long ldp, const void* WPs, const float* dY, long sdYb, float* dX, long sdXb,
@@ -173,7 +160,7 @@ int rcot_conv1x1_dgrad_wgrad_slabs(const float* WP, long ldp, const void* WPs, c
     if (prec != RCOT_PREC_BF16X3 || !WPs || B > 65535) return RCOT_EUNSUPPORTED;
     const int rc = pair_dgrad_wgrad_x3(WP, ldp, WPs, dY, sdYb, dX, sdXb, X, sXb, B, Ci, Co, N, ln_mu, ln_rs, ln_w, ln_b, ws, ws_bytes,
                                        ws_slabs, ws_slabs_bytes, S, ldws, (hipStream_t)stream);
-    return rc == -100 ? RCOT_EUNSUPPORTED : rc;
+    return rc == NOT_ELIGIBLE ? RCOT_EUNSUPPORTED : rc;
 }
 
 int rcot_bmm_nn(const float* A, long lda, long sAo, long sAi, int transA, const float* Bm, long ldb, long sBo,
@@ -208,7 +195,7 @@ int rcot_bmm_nt(const float* A, long lda, long sAo, long sAi, const float* Bm, l
     ep.sCo = sCo; ep.sCi = sCi;
     const int rc = try_gemm_nt_glds(M, N, K, Zo, Zi, A, lda, sAo, sAi, Bm, ldb, sBo, sBi, 0, 0, 0, nullptr, nullptr, 0, nullptr,
                                     nullptr, ep, ws, ws_bytes, (hipStream_t)stream, prec);
-    if (rc != -100) return rc;
+    if (rc != NOT_ELIGIBLE) return rc;
     return run_kcontig(d, ap, bp, ep, Zo * Zi, ws, ws_bytes, (hipStream_t)stream);
 }
 
@@ -220,7 +207,7 @@ int rcot_bmm_nt_slabs(const float* A, long lda, long sAo, long sAi, const float*
     EpiP ep{};
     const int rc = try_gemm_nt_glds(M, N, K, Zo, Zi, A, lda, sAo, sAi, Bm, ldb, sBo, sBi, 0, 0, 0, nullptr, nullptr, 0, nullptr,
                                     nullptr, ep, ws, ws_bytes, (hipStream_t)stream, prec, S, ldws);
-    return rc == -100 ? RCOT_EUNSUPPORTED : rc;
+    return rc == NOT_ELIGIBLE ? RCOT_EUNSUPPORTED : rc;
 }
 
 int rcot_linear_fwd(const float* X, const float* W, const float* bias, float* Y, int B, int in, int out, float lrelu,

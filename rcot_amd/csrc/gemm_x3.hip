@@ -29,6 +29,7 @@
 // c1, c2 by rcot_pack_weights) and the per-pixel statistics enter once, in the epilogue.  The four VALU operations per
 // B element that the in-loop normalisation costs (as many as the bf16 split itself) disappear from the slab loop.
 #include "gemm_core.h"
+#include "dispatch.h"
 #include "../../include/rcot_hip.h"
 
 using namespace rcot;
@@ -37,10 +38,6 @@ namespace rcot_x3 {
 
 typedef __attribute__((address_space(1))) const void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #ifndef X3_NST
 #define X3_NST 3
@@ -68,8 +65,6 @@ extern "C" int rcot_x3_set_trace(void* q) { g_x3_trace = (unsigned long long*)q;
 #else
 #define X3_STAMP(i) do {} while (0)
 #endif
-
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // wait until at most y slabs (PW vm operations each) of this wave are still in flight; y is wave-uniform, 0 <= y < NST
 template <int PW, int NST>
@@ -438,20 +433,18 @@ int launch_x3(X3P p, bool ln, int Z, hipStream_t st, size_t ws_bytes) {
     return RCOT_OK;
 }
 
-inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 }  // namespace rcot_x3
 
 namespace rcot {
 
-// Returns RCOT_OK after launching, or -100 when the shape is not eligible (the caller then uses the fp32 kernels).
+// Returns RCOT_OK after launching, or NOT_ELIGIBLE when the shape is not eligible (the caller then uses the fp32 kernels).
 int try_gemm_kmajor_x3(const float* At, long lda, long sAo, long sAi, const float* Bm, long ldb, long sBo, long sBi,
                        const EpiP& ep, const float* ln_mu, const float* ln_rs, long sLN, const float* ln_c1,
                        const float* ln_c2, int Zo, int Zi, int M, int N, int K, float* ws, size_t ws_bytes, hipStream_t st) {
     using namespace rcot_x3;
-    if ((N % 128) || K < 17) return -100;          // the slab ring needs at least two slabs per tile
+    if ((N % 128) || K < 17) return NOT_ELIGIBLE;          // the slab ring needs at least two slabs per tile
     const bool ln = ln_mu != nullptr;
-    if (ln && ((sLN & 3) || !al16(ln_mu) || !al16(ln_rs) || !ln_c1 || !ln_c2)) return -100;
+    if (ln && ((sLN & 3) || !al16(ln_mu) || !al16(ln_rs) || !ln_c1 || !ln_c2)) return NOT_ELIGIBLE;
     X3P p{};
     p.M = M; p.N = N; p.K = K; p.Zi = Zi;
     p.At = At; p.lda = lda; p.sAo = sAo; p.sAi = sAi;

@@ -21,17 +21,13 @@
 #include <type_traits>
 #include "gemm_core.h"
 #include "gemm_nt_body.h"
+#include "dispatch.h"
 #include "../../include/rcot_hip.h"
 
 using namespace rcot;
 
 namespace rcot_x3w {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 struct P {
@@ -67,8 +63,6 @@ extern "C" int rcot_x3w_set_trace(void* q) { g_x3w_trace = (unsigned long long*)
 #define X3_STAMP(i) do {} while (0)
 #endif
 
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 // wait until at most y slabs (PW vm operations each) are still in flight; y is wave-uniform, 0 <= y < NST
 template <int PW, int NST>
 __device__ __forceinline__ void wait_slabs(int y) {
@@ -85,11 +79,6 @@ template <int OFF>
 __device__ __forceinline__ void dma_piece(unsigned stage, const void* sbase, unsigned voff) {
     asm volatile("s_add_u32 m0, %0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3"
                  :: "s"(stage), "n"(OFF), "v"(voff), "s"(sbase) : "memory", "scc");
-}
-
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {                      // v_cvt_pk_bf16_f32 (rne): a -> low half
-    const f32x2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
 }
 
 // Split of the B fragment.  x[kk] = columns 4lm..4lm+3 of row 8kg+kk.  For a row pair (kk, kk+1) and a column pair the
@@ -800,23 +789,21 @@ int launch_conv(P p, hipStream_t st, size_t ws_bytes) {
     return RCOT_OK;
 }
 
-inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 }  // namespace rcot_x3w
 
 namespace rcot {
 
-// Returns RCOT_OK after launching, or -100 when the shape is not eligible (the caller then uses another kernel).
+// Returns RCOT_OK after launching, or NOT_ELIGIBLE when the shape is not eligible (the caller then uses another kernel).
 // Apk (optional): the pre-split form of At (rcot_pack_weight), only for batch-invariant A (sAo == sAi == 0).
 int try_gemm_kmajor_x3w(const float* At, long lda, long sAo, long sAi, const void* Apk, const float* Bm, long ldb, long sBo,
                         long sBi, const EpiP& ep, const float* ln_mu, const float* ln_rs, long sLN, const float* ln_c1,
                         const float* ln_c2, int Zo, int Zi, int M, int N, int K, float* ws, size_t ws_bytes, hipStream_t st,
                         bool ln_compute, int nterms) {
     using namespace rcot_x3w;
-    if ((N % 128) || K < 17) return -100;          // the slab ring needs at least two slabs per tile
-    if ((unsigned long)ldb * 4ul * 17ul >= (1ul << 32)) return -100;   // 32-bit per-lane DMA offsets
+    if ((N % 128) || K < 17) return NOT_ELIGIBLE;          // the slab ring needs at least two slabs per tile
+    if ((unsigned long)ldb * 4ul * 17ul >= (1ul << 32)) return NOT_ELIGIBLE;   // 32-bit per-lane DMA offsets
     const bool ln = ln_mu != nullptr;
-    if (ln && ((sLN & 3) || !al16(ln_mu) || !al16(ln_rs) || !ln_c1 || !ln_c2 || !al16(ln_c1) || !al16(ln_c2))) return -100;
+    if (ln && ((sLN & 3) || !al16(ln_mu) || !al16(ln_rs) || !ln_c1 || !ln_c2 || !al16(ln_c1) || !al16(ln_c2))) return NOT_ELIGIBLE;
     P p{};
     p.M = M; p.N = N; p.K = K; p.Zi = Zi;
     p.At = At; p.lda = lda; p.sAo = sAo; p.sAi = sAi;
@@ -831,10 +818,10 @@ int try_gemm_kmajor_x3w(const float* At, long lda, long sAo, long sAi, const voi
     p.trace = g_x3w_trace;
 #endif
     const int Z = Zo * Zi;
-    if (ln_compute && (!ln || Zi != 1)) return -100;
+    if (ln_compute && (!ln || Zi != 1)) return NOT_ELIGIBLE;
     if (!p.Apk || (N % 128) || M <= 64 || ep.alpha != 1.f || ep.rowscale || (long)M * ep.ldc >= (1l << 31) ||
         (long)M * N >= (1l << 31) || (ep.R && (long)M * ep.ldr >= (1l << 31)))
-        return -100;
+        return NOT_ELIGIBLE;
     // Tile form by occupancy (round 5, profiles/r05_x3p_tile_forms_x6_x3.txt): 128 x 256 tiles leave half the chip idle when a product has
     // 48..200 of them (the small planes: 2042 <- 384 at 8 x 16x16 is 128 tiles) — 128 x 128 tiles double the workgroups: 24.2 -> 17.6 us
     // there, 29.0 -> 21.5 us for the data gradient of 510 <- 96 at 64x64 (bf16x3; bf16x6 34.6 -> 26.4, 45.2 -> 32.8).  Fewer than 48
@@ -853,7 +840,7 @@ int try_gemm_kmajor_x3w(const float* At, long lda, long sAo, long sAi, const voi
 }
 
 // dX[b] (Ci x N) = W^T dY[b] on the pre-split pack WPs of W, and the split-K slabs of dW = sum_b dY[b] LN?(X[b])^T, in ONE launch
-// (x3p_nt_pair_kernel).  -100: one of the two products is not eligible for its kernel (the caller runs them separately).
+// (x3p_nt_pair_kernel).  NOT_ELIGIBLE: one of the two products is not eligible for its kernel (the caller runs them separately).
 int pair_dgrad_wgrad_x3(const float* WP, long ldp, const void* WPs, const float* dY, long sdYb, float* dX, long sdXb, const float* X,
                         long sXb, int B, int Ci, int Co, int N, const float* ln_mu, const float* ln_rs, const float* ln_w,
                         const float* ln_b, float* ws, size_t ws_bytes, float* ws_slabs, size_t ws_slabs_bytes, int* S_out,
@@ -864,8 +851,8 @@ int pair_dgrad_wgrad_x3(const float* WP, long ldp, const void* WPs, const float*
     // both products are bandwidth-bound and the pair is SLOWER than the two launches (893 -> 925 us): planes above 4096 pixels
     // keep the separate launches (weight gradient on the side stream)
     constexpr int pair_maxn = 4096;
-    if (N > pair_maxn) return -100;
-    if (!WPs || (N % 128) || K < 17 || M <= 64 || (long)M * N >= (1l << 31) || (unsigned long)N * 4ul * 17ul >= (1ul << 32)) return -100;
+    if (N > pair_maxn) return NOT_ELIGIBLE;
+    if (!WPs || (N % 128) || K < 17 || M <= 64 || (long)M * N >= (1l << 31) || (unsigned long)N * 4ul * 17ul >= (1ul << 32)) return NOT_ELIGIBLE;
     P p{};
     p.M = M; p.N = N; p.K = K; p.Zi = 1;
     p.At = WP; p.lda = ldp;
@@ -880,12 +867,12 @@ int pair_dgrad_wgrad_x3(const float* WP, long ldp, const void* WPs, const float*
     int nA = 0;
     size_t smemA = 0;
     constexpr int slotsA = 256, slotsB = 320;       // workgroup slots each product's split aims at
-    if (configure_p<1, 3>(p, false, B, ws_bytes, false, &nA, &smemA, slotsA) != RCOT_OK) return -100;
+    if (configure_p<1, 3>(p, false, B, ws_bytes, false, &nA, &smemA, slotsA) != RCOT_OK) return NOT_ELIGIBLE;
     rcot_nt::NTP q{};
     int cfg = 0;
     if (nt_configure(Co, Ci, B * N, 1, 1, dY, N, 0, 0, X, N, 0, 0, N, sdYb, sXb, ln_mu, ln_rs, N, ln_w, ln_b, ws_slabs, ws_slabs_bytes, 1, 0,
                      &q, &cfg, slotsB) != RCOT_OK)
-        return -100;
+        return NOT_ELIGIBLE;
     *S_out = q.S;
     *ld_out = q.ldws;
     int rc;

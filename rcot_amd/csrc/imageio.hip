@@ -18,8 +18,6 @@ constexpr int TILE = 256;                               // pixels of one row per
 constexpr int ROWS = 4;                                 // waves (image rows) per workgroup
 constexpr int LW = (4 + 3 + 3 * (TILE + 1) + 3) / 4 + 1;   // LDS words of one staged row segment: offset 4 + phase <= 3 + halo pixel + TILE pixels
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // source row / column of padded row / column r of an n-long axis: torch's 'reflect' (mode 1) or 'replicate' (mode 2)
 __device__ __forceinline__ int src_index(int r, int n, int mode) { return r < n ? r : (mode == 1 ? 2 * (n - 1) - r : n - 1); }
 
@@ -314,35 +312,16 @@ __global__ __launch_bounds__(256) void egress_kernel(EgressArgs a) {
     }
 }
 
-// stats[0..4) from the partials, one workgroup, fixed order: strided per-thread sums, then a tree over the 256 threads
+// stats[0..4) from the partials, one workgroup, fixed order (final_sums)
 __global__ __launch_bounds__(256) void egress_final_kernel(const double* __restrict__ part_d, const long long* __restrict__ part_i, long nb,
                                                            int h, int w, double* __restrict__ stats) {
-    __shared__ double sf[256], ss[256];
-    __shared__ long long si[256];
-    const int t = threadIdx.x;
-    double f = 0.0, s = 0.0;
-    long long n = 0;
-    for (long b = t; b < nb; b += 256) {
-        f += part_d[b];
-        s += part_d[nb + b];
-        n += part_i[b];
-    }
-    sf[t] = f;
-    ss[t] = s;
-    si[t] = n;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (t < o) {
-            sf[t] += sf[t + o];
-            ss[t] += ss[t + o];
-            si[t] += si[t + o];
-        }
-        __syncthreads();
-    }
-    if (t == 0) {
-        stats[0] = sf[0];
-        stats[1] = (double)si[0];
-        stats[2] = ss[0];
+    double d[2];
+    long long n;
+    final_sums<2>(part_d, part_i, nb, d, n);
+    if (threadIdx.x == 0) {
+        stats[0] = d[0];
+        stats[1] = (double)n;
+        stats[2] = d[1];
         stats[3] = 3.0 * (double)(h > 10 ? h - 10 : 0) * (double)(w > 10 ? w - 10 : 0);
     }
 }

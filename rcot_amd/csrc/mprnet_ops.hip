@@ -10,13 +10,6 @@ using namespace rcot;
 
 namespace {
 
-inline int grid_for(long n, int bs = 256, int cap = 8192) {
-    long g = (n + bs - 1) / bs;
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // ------------------------------------------------------------------ PReLU with ONE learnable slope (nn.PReLU(), Net.py:185)
 // y = x > 0 ? x : a x.  nv float4 groups, then the scalar tail [4 nv, n).
 // (y may be x: no __restrict__ on the pair)

@@ -6,6 +6,8 @@
 
 namespace {
 
+using rcot::al16;
+
 __global__ __launch_bounds__(256) void rmsprop_kernel(float4* __restrict__ p, const float4* __restrict__ g,
                                                       float4* __restrict__ sq, long n4, float lr, float alpha, float oma,
                                                       float eps, float gscale) {
@@ -44,9 +46,6 @@ __global__ __launch_bounds__(256) void adam_kernel(float4* __restrict__ p, const
         v[i] = vv;
     }
 }
-
-inline bool ok16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -55,7 +54,7 @@ extern "C" {
 // precision exactly as torch.optim does on the host (1 - 0.999f would be off by 1.3e-5 relative).
 int rcot_rmsprop_step(float* p, const float* g, float* sq, long n, double lr, double alpha, double eps,
                       double grad_scale, void* stream) {
-    if (!p || !g || !sq || n <= 0 || (n & 3) || !ok16(p) || !ok16(g) || !ok16(sq)) return RCOT_EINVAL;
+    if (!p || !g || !sq || n <= 0 || (n & 3) || !al16(p) || !al16(g) || !al16(sq)) return RCOT_EINVAL;
     const long n4 = n >> 2;
     long grid = (n4 + 255) / 256;
     if (grid > 4096) grid = 4096;
@@ -67,7 +66,7 @@ int rcot_rmsprop_step(float* p, const float* g, float* sq, long n, double lr, do
 
 int rcot_adam_step(float* p, const float* g, float* m, float* v, long n, double lr, double b1, double b2, double eps,
                    int step, double grad_scale, void* stream) {
-    if (!p || !g || !m || !v || n <= 0 || (n & 3) || step <= 0 || !ok16(p) || !ok16(g) || !ok16(m) || !ok16(v))
+    if (!p || !g || !m || !v || n <= 0 || (n & 3) || step <= 0 || !al16(p) || !al16(g) || !al16(m) || !al16(v))
         return RCOT_EINVAL;
     const long n4 = n >> 2;
     long grid = (n4 + 255) / 256;

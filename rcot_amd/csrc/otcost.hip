@@ -5,9 +5,10 @@
 //   loss_T   += sigma*(rmse + sum_i f_i) [+ Sigma*mean|T(x)-y|]
 // Elementwise / bandwidth-bound work, no MFMA.  The spectrum branch runs three line-FFT passes
 // (rows forward; columns forward -> |F|, F/|F| -> columns inverse; rows inverse) over an L2-resident
-// complex scratch; each wavefront owns one line in LDS.  The line transform is chosen per axis by rcot_fft_plan (rows: W,
-// columns: H): powers of two run the in-place radix-2 fft_line; lengths with prime factors <= 13 a mixed-radix Stockham
-// autosort between two LDS buffers; every other length <= 1024 Bluestein's chirp-z over three radix-2 transforms.
+// complex scratch; each wavefront owns one line in LDS.  Each pass is one kernel template over the line transform (LineKind),
+// chosen per axis by rcot_fft_plan (rows: W, columns: H): powers of two run the in-place radix-2 fft_line; lengths with prime
+// factors <= 13 a mixed-radix Stockham autosort between two LDS buffers; every other length <= 1024 Bluestein's chirp-z over
+// three radix-2 transforms.
 #include "common.h"
 #include "../../include/rcot_hip.h"
 
@@ -66,83 +67,21 @@ __global__ __launch_bounds__(256) void ot_reduce_kernel(const float* __restrict_
     }
 }
 
-// pass 1: forward FFT of every row of res (planes of samples with de_id >= 3 only)
-__global__ __launch_bounds__(256) void ot_rows_fwd_kernel(const float* __restrict__ deg, const float* __restrict__ out,
-                                                          const int* __restrict__ de_id, float2* __restrict__ scr,
-                                                          int H, int W, int logW) {
-    extern __shared__ __attribute__((aligned(16))) float2 sm[];
-    const int plane = blockIdx.y, b = plane / 3;
-    if (de_id[b] < 3) return;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int row = blockIdx.x * LPB + wave;
-    float2* line = sm + wave * W;
-    const long base = ((long)plane * H + row) * W;
-    if (row < H)
-        for (int i = lane; i < W; i += 64) line[i] = make_float2(deg[base + i] - out[base + i], 0.f);
-    __syncthreads();
-    fft_line(line, W, logW, -1.f, lane);
-    if (row < H)
-        for (int i = lane; i < W; i += 64) scr[base + i] = line[i];
-}
-
-// pass 2: forward FFT of every column -> |F| (sum into spec[b]) and U = F/|F| -> inverse FFT along the column
-__global__ __launch_bounds__(256) void ot_cols_kernel(const int* __restrict__ de_id, float2* __restrict__ scr,
-                                                      float* __restrict__ spec, int H, int W, int logH) {
-    extern __shared__ __attribute__((aligned(16))) float2 sm[];
-    __shared__ float red[4];
-    const int plane = blockIdx.y, b = plane / 3;
-    if (de_id[b] < 3) return;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int col = blockIdx.x * LPB + wave;
-    float2* line = sm + wave * H;
-    float2* p = scr + (long)plane * H * W + col;
-    if (col < W)
-        for (int i = lane; i < H; i += 64) line[i] = p[(long)i * W];
-    __syncthreads();
-    fft_line(line, H, logH, -1.f, lane);
-    float s = 0.f;
-    if (col < W)
-        for (int i = lane; i < H; i += 64) {
-            const float2 f = line[i];
-            const float mag = sqrtf(f.x * f.x + f.y * f.y);
-            s += mag;
-            line[i] = mag > 0.f ? make_float2(f.x / mag, f.y / mag) : make_float2(0.f, 0.f);
-        }
-    s = block_sum<256>(s, red);
-    if (threadIdx.x == 0) atomicAdd(&spec[b], s);
-    __syncthreads();
-    fft_line(line, H, logH, 1.f, lane);
-    if (col < W)
-        for (int i = lane; i < H; i += 64) p[(long)i * W] = line[i];
-}
-
-// pass 3: inverse FFT of every row; gF = Re(.) / (3*H*W)   ( == Re(ifft2(U)) / 3 )
-__global__ __launch_bounds__(256) void ot_rows_inv_kernel(const int* __restrict__ de_id, const float2* __restrict__ scr,
-                                                          float* __restrict__ gF, int H, int W, int logW) {
-    extern __shared__ __attribute__((aligned(16))) float2 sm[];
-    const int plane = blockIdx.y, b = plane / 3;
-    if (de_id[b] < 3) return;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int row = blockIdx.x * LPB + wave;
-    float2* line = sm + wave * W;
-    const long base = ((long)plane * H + row) * W;
-    if (row < H)
-        for (int i = lane; i < W; i += 64) line[i] = scr[base + i];
-    __syncthreads();
-    fft_line(line, W, logW, 1.f, lane);
-    const float sc = 1.0f / (3.0f * (float)H * (float)W);
-    if (row < H)
-        for (int i = lane; i < W; i += 64) gF[base + i] = line[i].x * sc;
-}
-
-// ---- line transforms for lengths that are not powers of two ------------------------------------------------------------------
+// ---- line transforms: one per LineKind ---------------------------------------------------------------------------------------
 constexpr int MAXST = 10;          // stages of a plan (rcot_fft_plan): 2 * 3^5 = 486 needs 6, 2^10 needs 10
+constexpr int MAXMR = 8;           // radices a LinePlan stores (see there)
 
-// How one axis is transformed; passed by value to the kernels.  ns > 0: mixed radix, rad[0..ns) with product n.
-// ns == 0: Bluestein over the power of two M = 1 << logM >= 2n - 1.
+enum LineKind { RADIX2, MIXED, BLUESTEIN };
+
+// How one axis is transformed; passed by value to the kernels.  RADIX2: n = 1 << ns, fft_line in place (rad unused).  MIXED:
+// rad[0..ns) with product n.  BLUESTEIN (ns == 0): over the power of two M = 1 << logM >= 2n - 1.  kind and lds (float2 of LDS
+// one wavefront needs for one line: n, 2n, M) are for the host's dispatch.  rad[] holds MAXMR = 8 radices, not MAXST: only mixed
+// plans read it and none up to MAXP has more than 6 stages (2 * 3^5), and with the two host fields the struct then keeps the
+// 56 bytes it had, so bs_filter_kernel's kernarg segment and descriptor stay what they were.
 struct LinePlan {
     int n, ns, M, logM;
-    int rad[MAXST];
+    int rad[MAXMR];
+    int kind, lds;
 };
 
 // One Stockham stage of radix R (decimation in time): src viewed as [R][n/(R L)][L] -> dst [n/(R L)][R][L], L = product of the
@@ -247,19 +186,25 @@ __device__ void bs_line(float2* line, const LinePlan& p, float sign, int lane, c
     __syncthreads();
 }
 
-template <bool BS>
+// p.lds on the device, from n / M: with W, H and the pointers these sit in the first 64 bytes of the kernarg segment, so a radix-2
+// pass loads no more of it than when it took one integer (p.lds lies in the second cache line: a miss per launch)
+template <int KIND>
+__device__ __forceinline__ int line_lds(const LinePlan& p) { return KIND == RADIX2 ? p.n : (KIND == MIXED ? 2 * p.n : p.M); }
+
+// Transform of the line at `cur` inside this wavefront's buf[p.lds]; returns where the result is.
+template <int KIND>
 __device__ __forceinline__ float2* line_fft(float2* buf, float2* cur, const LinePlan& p, float sign, int lane,
                                             const float2* __restrict__ filt) {
-    if constexpr (BS) {
+    if constexpr (KIND == RADIX2) {
+        fft_line(buf, p.n, p.ns, sign, lane);
+        return buf;
+    } else if constexpr (KIND == BLUESTEIN) {
         bs_line(buf, p, sign, lane, filt);
         return buf;
     } else {
         return mr_line(buf, cur, p, sign, lane);
     }
 }
-
-// float2 of LDS one wavefront needs for one line
-__host__ __device__ inline int line_lds(const LinePlan& p) { return p.ns ? 2 * p.n : p.M; }
 
 // The transformed chirp filter of one Bluestein length, once per call: filt[0..M) = FFT_M(b) / M, b_k = b_{M-k} = exp(+i pi k^2/n)
 // for k < n, zero between.  One wavefront.
@@ -276,39 +221,47 @@ __global__ __launch_bounds__(64) void bs_filter_kernel(float2* __restrict__ filt
     for (int i = lane; i < p.M; i += 64) filt[i] = make_float2(sm[i].x * sc, sm[i].y * sc);
 }
 
-// The three passes again, over a LinePlan instead of a radix-2 length (same launch geometry, same scratch layout).
-template <bool BS>
-__device__ __forceinline__ void rows_fwd_body(const float* __restrict__ deg, const float* __restrict__ out,
-                                              const int* __restrict__ de_id, float2* __restrict__ scr, int H, int W,
-                                              const LinePlan& p, const float2* __restrict__ filt) {
+// pass 1: forward FFT of every row of res (planes of samples with de_id >= 3 only).  Lines of a block beyond H / W are zero.
+template <int KIND>
+__global__ __launch_bounds__(256) void ot_rows_fwd_kernel(const float* __restrict__ deg, const float* __restrict__ out,
+                                                          const int* __restrict__ de_id, float2* __restrict__ scr, int H,
+                                                          int W, LinePlan p, const float2* __restrict__ filt) {
     extern __shared__ __attribute__((aligned(16))) float2 sm[];
     const int plane = blockIdx.y, b = plane / 3;
     if (de_id[b] < 3) return;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int row = blockIdx.x * LPB + wave;
-    float2* line = sm + wave * line_lds(p);
+    float2* line = sm + wave * line_lds<KIND>(p);
     const long base = ((long)plane * H + row) * W;
-    for (int i = lane; i < W; i += 64) line[i] = row < H ? make_float2(deg[base + i] - out[base + i], 0.f) : make_float2(0.f, 0.f);
+    if (row < H)
+        for (int i = lane; i < W; i += 64) line[i] = make_float2(deg[base + i] - out[base + i], 0.f);
+    else
+        for (int i = lane; i < W; i += 64) line[i] = make_float2(0.f, 0.f);
     __syncthreads();
-    const float2* r = line_fft<BS>(line, line, p, -1.f, lane, filt);
+    const float2* r = line_fft<KIND>(line, line, p, -1.f, lane, filt);
     if (row < H)
         for (int i = lane; i < W; i += 64) scr[base + i] = r[i];
 }
 
-template <bool BS>
-__device__ __forceinline__ void cols_body(const int* __restrict__ de_id, float2* __restrict__ scr, float* __restrict__ spec,
-                                          int H, int W, const LinePlan& p, const float2* __restrict__ filt) {
+// pass 2: forward FFT of every column -> |F| (sum into spec[b]) and U = F/|F| -> inverse FFT along the column
+template <int KIND>
+__global__ __launch_bounds__(256) void ot_cols_kernel(const int* __restrict__ de_id, float2* __restrict__ scr,
+                                                      float* __restrict__ spec, int H, int W, LinePlan p,
+                                                      const float2* __restrict__ filt) {
     extern __shared__ __attribute__((aligned(16))) float2 sm[];
     __shared__ float red[4];
     const int plane = blockIdx.y, b = plane / 3;
     if (de_id[b] < 3) return;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int col = blockIdx.x * LPB + wave;
-    float2* line = sm + wave * line_lds(p);
+    float2* line = sm + wave * line_lds<KIND>(p);
     float2* g = scr + (long)plane * H * W + col;
-    for (int i = lane; i < H; i += 64) line[i] = col < W ? g[(long)i * W] : make_float2(0.f, 0.f);
+    if (col < W)
+        for (int i = lane; i < H; i += 64) line[i] = g[(long)i * W];
+    else
+        for (int i = lane; i < H; i += 64) line[i] = make_float2(0.f, 0.f);
     __syncthreads();
-    float2* f = line_fft<BS>(line, line, p, -1.f, lane, filt);
+    float2* f = line_fft<KIND>(line, line, p, -1.f, lane, filt);
     float s = 0.f;
     if (col < W)
         for (int i = lane; i < H; i += 64) {
@@ -320,50 +273,33 @@ __device__ __forceinline__ void cols_body(const int* __restrict__ de_id, float2*
     s = block_sum<256>(s, red);
     if (threadIdx.x == 0) atomicAdd(&spec[b], s);
     __syncthreads();
-    const float2* r = line_fft<BS>(line, f, p, 1.f, lane, filt);
+    const float2* r = line_fft<KIND>(line, f, p, 1.f, lane, filt);
     if (col < W)
         for (int i = lane; i < H; i += 64) g[(long)i * W] = r[i];
 }
 
-template <bool BS>
-__device__ __forceinline__ void rows_inv_body(const int* __restrict__ de_id, const float2* __restrict__ scr,
-                                              float* __restrict__ gF, int H, int W, const LinePlan& p,
-                                              const float2* __restrict__ filt) {
+// pass 3: inverse FFT of every row; gF = Re(.) / (3*H*W)   ( == Re(ifft2(U)) / 3 )
+template <int KIND>
+__global__ __launch_bounds__(256) void ot_rows_inv_kernel(const int* __restrict__ de_id, const float2* __restrict__ scr,
+                                                          float* __restrict__ gF, int H, int W, LinePlan p,
+                                                          const float2* __restrict__ filt) {
     extern __shared__ __attribute__((aligned(16))) float2 sm[];
     const int plane = blockIdx.y, b = plane / 3;
     if (de_id[b] < 3) return;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int row = blockIdx.x * LPB + wave;
-    float2* line = sm + wave * line_lds(p);
+    float2* line = sm + wave * line_lds<KIND>(p);
     const long base = ((long)plane * H + row) * W;
-    for (int i = lane; i < W; i += 64) line[i] = row < H ? scr[base + i] : make_float2(0.f, 0.f);
+    if (row < H)
+        for (int i = lane; i < W; i += 64) line[i] = scr[base + i];
+    else
+        for (int i = lane; i < W; i += 64) line[i] = make_float2(0.f, 0.f);
     __syncthreads();
-    const float2* r = line_fft<BS>(line, line, p, 1.f, lane, filt);
+    const float2* r = line_fft<KIND>(line, line, p, 1.f, lane, filt);
     const float sc = 1.0f / (3.0f * (float)H * (float)W);
     if (row < H)
         for (int i = lane; i < W; i += 64) gF[base + i] = r[i].x * sc;
 }
-
-#define RCOT_OT_LINE_KERNELS(sfx, BS)                                                                                          \
-    __global__ __launch_bounds__(256) void ot_rows_fwd_##sfx##_kernel(                                                         \
-        const float* __restrict__ deg, const float* __restrict__ out, const int* __restrict__ de_id, float2* __restrict__ scr, \
-        int H, int W, LinePlan p, const float2* __restrict__ filt) {                                                           \
-        rows_fwd_body<BS>(deg, out, de_id, scr, H, W, p, filt);                                                                \
-    }                                                                                                                          \
-    __global__ __launch_bounds__(256) void ot_cols_##sfx##_kernel(const int* __restrict__ de_id, float2* __restrict__ scr,     \
-                                                                  float* __restrict__ spec, int H, int W, LinePlan p,          \
-                                                                  const float2* __restrict__ filt) {                           \
-        cols_body<BS>(de_id, scr, spec, H, W, p, filt);                                                                        \
-    }                                                                                                                          \
-    __global__ __launch_bounds__(256) void ot_rows_inv_##sfx##_kernel(const int* __restrict__ de_id,                           \
-                                                                      const float2* __restrict__ scr, float* __restrict__ gF,  \
-                                                                      int H, int W, LinePlan p,                                \
-                                                                      const float2* __restrict__ filt) {                       \
-        rows_inv_body<BS>(de_id, scr, gF, H, W, p, filt);                                                                      \
-    }
-RCOT_OT_LINE_KERNELS(mixed, false)
-RCOT_OT_LINE_KERNELS(bluestein, true)
-#undef RCOT_OT_LINE_KERNELS
 
 // dout += -sigma*( res/(Mg*rmse) + [de_id<3 ? res/3 : gF] ) + Sigma*sign(out-tgt)/Mg
 // scal[0]=rmse (global), scal[1]=local Fourier penalty sum, scal[2]=local sum|out-tgt| / Mg
@@ -398,8 +334,8 @@ __global__ __launch_bounds__(256) void ot_grad_kernel(const float* __restrict__ 
     }
 }
 
-// Host side of a LinePlan: what rcot_fft_plan answers for n.  kind: 0 radix-2 (today's kernels), 1 mixed radix, 2 Bluestein.
-int make_plan(int n, LinePlan& p, int& kind) {
+// Host side of a LinePlan: what rcot_fft_plan answers for n.
+int make_plan(int n, LinePlan& p) {
     int rad[MAXST];
     const int ns = rcot_fft_plan(n, rad, MAXST);
     if (ns < 0) return ns;
@@ -407,15 +343,32 @@ int make_plan(int n, LinePlan& p, int& kind) {
     p.ns = ns;
     p.M = p.logM = 0;
     bool two = ns > 0;
-    for (int i = 0; i < MAXST; ++i) {
-        p.rad[i] = i < ns ? rad[i] : 1;
-        if (i < ns && rad[i] != 2) two = false;
-    }
+    for (int i = 0; i < ns; ++i)
+        if (rad[i] != 2) two = false;
+    for (int i = 0; i < MAXMR; ++i) p.rad[i] = i < ns ? rad[i] : 1;
     if (ns == 0) {
         p.M = rad[0];
         while ((1 << p.logM) < p.M) ++p.logM;
     }
-    kind = two ? 0 : (ns > 0 ? 1 : 2);
+    p.kind = two ? RADIX2 : (ns > 0 ? MIXED : BLUESTEIN);
+    p.lds = two ? n : (ns > 0 ? 2 * n : p.M);
+    return RCOT_OK;
+}
+
+// The instantiations of the three passes, indexed by LineKind.
+#define RCOT_OT_KINDS(k) {k<RADIX2>, k<MIXED>, k<BLUESTEIN>}
+constexpr decltype(&ot_rows_fwd_kernel<RADIX2>) k_rows_fwd[3] = RCOT_OT_KINDS(ot_rows_fwd_kernel);
+constexpr decltype(&ot_cols_kernel<RADIX2>) k_cols[3] = RCOT_OT_KINDS(ot_cols_kernel);
+constexpr decltype(&ot_rows_inv_kernel<RADIX2>) k_rows_inv[3] = RCOT_OT_KINDS(ot_rows_inv_kernel);
+#undef RCOT_OT_KINDS
+const char* const k_rows_inv_name[3] = {"ot_rows_inv_kernel", "ot_rows_inv_mixed_kernel", "ot_rows_inv_bluestein_kernel"};
+
+// One pass over one axis: the instantiation of plan p's kind, LPB lines of p.lds per block; a... is what the kernel takes before
+// (p, filt).
+template <typename K, typename... A>
+int launch_pass(K* const (&k)[3], dim3 grid, hipStream_t st, const LinePlan& p, const float2* filt, A... a) {
+    RCOT_LAUNCH(k[p.kind], grid, dim3(256), sizeof(float2) * LPB * p.lds, st, a..., p, filt);
+    RCOT_LAUNCH_CHECK();
     return RCOT_OK;
 }
 
@@ -467,70 +420,49 @@ int rcot_ot_spectrum(const float* degraded, const float* restored, const int* de
                      size_t ws_bytes, int B, int H, int W, void* stream) {
     if (!degraded || !restored || !de_id || !gF || !spec || !ws || B <= 0 || B * 3 > 65535) return RCOT_EINVAL;
     LinePlan pw, ph;
-    int kw = 0, kh = 0;
-    int rc = make_plan(W, pw, kw);
-    if (rc == RCOT_OK) rc = make_plan(H, ph, kh);
+    int rc = make_plan(W, pw);
+    if (rc == RCOT_OK) rc = make_plan(H, ph);
     if (rc != RCOT_OK) return rc;
     // scratch, then the chirp filter of each axis that runs Bluestein
     const size_t n_scr = (size_t)B * 3 * H * W;
-    if (ws_bytes < sizeof(float2) * (n_scr + (kw == 2 ? pw.M : 0) + (kh == 2 ? ph.M : 0))) return RCOT_EWORKSPACE;
+    const size_t n_fw = pw.kind == BLUESTEIN ? pw.M : 0, n_fh = ph.kind == BLUESTEIN ? ph.M : 0;
+    if (ws_bytes < sizeof(float2) * (n_scr + n_fw + n_fh)) return RCOT_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipMemsetAsync(spec, 0, sizeof(float) * (size_t)B, st);
     if (e != hipSuccess) return (int)e;
     float2* scr = reinterpret_cast<float2*>(ws);
     float2* fw = scr + n_scr;
-    float2* fh = fw + (kw == 2 ? pw.M : 0);
-    if (kw | kh) {
+    float2* fh = fw + n_fw;
+    if (pw.kind != RADIX2 || ph.kind != RADIX2) {
         // LDS per block: 4 lines of 2n (mixed radix, n <= 1000) or M <= 2048 (Bluestein) complex values = up to 64 KiB, plus the
         // columns kernels' 16 static bytes: above the default limit of a launch
         // (a refusal here is not an error of its own: the launch below reports a size it cannot have)
         static const bool raised = [] {
             bool ok = true;
-            for (const void* k : {(const void*)ot_rows_fwd_mixed_kernel, (const void*)ot_cols_mixed_kernel,
-                                  (const void*)ot_rows_inv_mixed_kernel, (const void*)ot_rows_fwd_bluestein_kernel,
-                                  (const void*)ot_cols_bluestein_kernel, (const void*)ot_rows_inv_bluestein_kernel})
-                if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess) {
-                    (void)hipGetLastError();
-                    ok = false;
-                }
+            for (int kind : {MIXED, BLUESTEIN})
+                for (const void* k : {(const void*)k_rows_fwd[kind], (const void*)k_cols[kind], (const void*)k_rows_inv[kind]})
+                    if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess) {
+                        (void)hipGetLastError();
+                        ok = false;
+                    }
             return ok;
         }();
         (void)raised;
     }
-    if (kw == 2) {
+    if (pw.kind == BLUESTEIN) {
         RCOT_LAUNCH(bs_filter_kernel, dim3(1), dim3(64), sizeof(float2) * pw.M, st, fw, pw);
         RCOT_LAUNCH_CHECK();
     }
-    if (kh == 2) {
+    if (ph.kind == BLUESTEIN) {
         RCOT_LAUNCH(bs_filter_kernel, dim3(1), dim3(64), sizeof(float2) * ph.M, st, fh, ph);
         RCOT_LAUNCH_CHECK();
     }
     const dim3 grows(cdiv(H, LPB), B * 3), gcols(cdiv(W, LPB), B * 3);
-    const size_t lw = sizeof(float2) * LPB * line_lds(pw), lh = sizeof(float2) * LPB * line_lds(ph);
-    if (kw == 0)
-        RCOT_LAUNCH(ot_rows_fwd_kernel, grows, dim3(256), sizeof(float2) * LPB * W, st, degraded, restored, de_id, scr, H, W,
-                    pw.ns);
-    else if (kw == 1)
-        RCOT_LAUNCH(ot_rows_fwd_mixed_kernel, grows, dim3(256), lw, st, degraded, restored, de_id, scr, H, W, pw, fw);
-    else
-        RCOT_LAUNCH(ot_rows_fwd_bluestein_kernel, grows, dim3(256), lw, st, degraded, restored, de_id, scr, H, W, pw, fw);
-    RCOT_LAUNCH_CHECK();
-    if (kh == 0)
-        RCOT_LAUNCH(ot_cols_kernel, gcols, dim3(256), sizeof(float2) * LPB * H, st, de_id, scr, spec, H, W, ph.ns);
-    else if (kh == 1)
-        RCOT_LAUNCH(ot_cols_mixed_kernel, gcols, dim3(256), lh, st, de_id, scr, spec, H, W, ph, fh);
-    else
-        RCOT_LAUNCH(ot_cols_bluestein_kernel, gcols, dim3(256), lh, st, de_id, scr, spec, H, W, ph, fh);
-    RCOT_LAUNCH_CHECK();
-    note_kernel("%s", kw == 0 ? "ot_rows_inv_kernel" : kw == 1 ? "ot_rows_inv_mixed_kernel" : "ot_rows_inv_bluestein_kernel");
-    if (kw == 0)
-        RCOT_LAUNCH(ot_rows_inv_kernel, grows, dim3(256), sizeof(float2) * LPB * W, st, de_id, scr, gF, H, W, pw.ns);
-    else if (kw == 1)
-        RCOT_LAUNCH(ot_rows_inv_mixed_kernel, grows, dim3(256), lw, st, de_id, scr, gF, H, W, pw, fw);
-    else
-        RCOT_LAUNCH(ot_rows_inv_bluestein_kernel, grows, dim3(256), lw, st, de_id, scr, gF, H, W, pw, fw);
-    RCOT_LAUNCH_CHECK();
-    return RCOT_OK;
+    rc = launch_pass(k_rows_fwd, grows, st, pw, fw, degraded, restored, de_id, scr, H, W);
+    if (rc == RCOT_OK) rc = launch_pass(k_cols, gcols, st, ph, fh, de_id, scr, spec, H, W);
+    if (rc != RCOT_OK) return rc;
+    note_kernel("%s", k_rows_inv_name[pw.kind]);
+    return launch_pass(k_rows_inv, grows, st, pw, fw, de_id, scr, gF, H, W);
 }
 
 int rcot_ot_grad(const float* degraded, const float* restored, const float* target, const int* de_id, const float* gF,

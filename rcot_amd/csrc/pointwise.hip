@@ -1173,13 +1173,6 @@ __global__ void pixel_shuffle_kernel(const float* __restrict__ in, float* __rest
 // consecutive lanes own consecutive pixel quads of one row and rows start at lane positions that are multiples of W/4
 inline bool nb_lanes_ok(int W) { const int wq = W >> 2; return (W & 3) == 0 && wq >= 1 && wq <= 64 && (64 % wq) == 0; }
 
-inline int grid_for(long n, int bs = 256, int cap = 8192) {
-    long g = (n + bs - 1) / bs;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 }  // namespace
 
 namespace {

@@ -228,33 +228,16 @@ __global__ __launch_bounds__(256) void quality_kernel(QualityArgs q) {
     }
 }
 
-// stats[0..4) from the partials, one workgroup, fixed order: strided per-thread sums, then a tree over the 256 threads
+// stats[0..4) from the partials, one workgroup, fixed order (final_sums)
 __global__ __launch_bounds__(256) void quality_final_kernel(const double* __restrict__ part_s, const long long* __restrict__ part_i, long nb,
                                                             double elements, double positions, double* __restrict__ stats) {
-    __shared__ double ss[256];
-    __shared__ long long si[256];
-    const int t = threadIdx.x;
-    double s = 0.0;
-    long long n = 0;
-#pragma unroll 8
-    for (long b = t; b < nb; b += 256) {                // the loads of eight steps in flight, the sums in order
-        s += part_s[b];
-        n += part_i[b];
-    }
-    ss[t] = s;
-    si[t] = n;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (t < o) {
-            ss[t] += ss[t + o];
-            si[t] += si[t + o];
-        }
-        __syncthreads();
-    }
-    if (t == 0) {
-        stats[0] = (double)si[0];
+    double d[1];
+    long long n;
+    final_sums<1>(part_s, part_i, nb, d, n);
+    if (threadIdx.x == 0) {
+        stats[0] = (double)n;
         stats[1] = elements;
-        stats[2] = ss[0];
+        stats[2] = d[0];
         stats[3] = positions;
     }
 }

@@ -1,5 +1,5 @@
-"""Time rcot_ot_spectrum alone over patch sizes: the radix-2 kernels at powers of two (the yardstick: unchanged code), the
-mixed-radix Stockham kernels at the sizes between them and Bluestein at 544 = 32 * 17.
+"""Time rcot_ot_spectrum alone over patch sizes: the radix-2 line transform at powers of two (the yardstick), the mixed-radix
+Stockham transform at the sizes between them and Bluestein at 544 = 32 * 17: three instantiations of the same pass kernels.
 
     python scripts/bench_ot_spectrum.py [--calls 200] [--batch 16] > profiles/ot_spectrum_sizes.txt
 

@@ -45,7 +45,8 @@ def _last_kernel(be):
 
 
 # ----------------------------------------------------------------------------- a. kernels vs fp64
-SIZES = [(96, 96), (160, 160), (224, 224), (96, 160), (352, 352), (136, 200), (6, 10), (1000, 24), (544, 544), (992, 96)]
+SIZES = [(96, 96), (160, 160), (224, 224), (96, 160), (352, 352), (136, 200), (6, 10), (1000, 24), (544, 544), (992, 96),
+         (2, 8), (8, 2), (64, 16)]      # radix-2 lines where a workgroup's four lines run past the image, or are few
 
 
 @pytest.mark.parametrize("H,W", SIZES)
@@ -152,7 +153,7 @@ def test_ot_cost_sizes_oracle_and_fixture(hip, gold, H, W):
 # ----------------------------------------------------------------------------- c. dispatch
 @pytest.mark.parametrize("H,W,symbol", [(128, 128, "ot_rows_inv_kernel"), (96, 96, "ot_rows_inv_mixed_kernel"),
                                         (544, 544, "ot_rows_inv_bluestein_kernel"), (96, 128, "ot_rows_inv_kernel"),
-                                        (128, 96, "ot_rows_inv_mixed_kernel")])
+                                        (128, 96, "ot_rows_inv_mixed_kernel"), (64, 16, "ot_rows_inv_kernel")])
 def test_dispatch_by_length(hip, H, W, symbol):
     """The rows passes follow W's plan, the columns pass H's: the last launch of a call is the inverse rows pass."""
     B = 1
