@@ -25,7 +25,7 @@ extern "C" {
 
 /* Bumped on EVERY signature change; returned by rcot_abi_version() (csrc/api.hip) and compared by the loader
  * (rcot_amd/lib.py ABI_VERSION, tests/test_abi.py) so that a stale prebuilt .so is refused, not mis-called. */
-#define RCOT_ABI_VERSION 28
+#define RCOT_ABI_VERSION 29
 
 /* Arithmetic of the MFMA products of the three GEMM-shaped entry points that take `prec` (rcot_gemm_kmajor,
  * rcot_conv1x1_wgrad, rcot_bmm_nt); operands and results are fp32 in memory either way.
@@ -486,6 +486,34 @@ int rcot_image_egress(const float* restored, const float* degraded, const unsign
  *                       misaligned: RCOT_EWORKSPACE, nothing is launched and stats is untouched. */
 int rcot_image_quality(const unsigned char* a, const unsigned char* b, int h, int w, int window, int space, double* stats, float* ws,
                        size_t ws_bytes, void* stream);
+
+/* ---- views of an image and their weighted blend (csrc/views.hip; rcot_amd/tiles.py, the tester's --tile / --ensemble) -----------------
+ * Tiled inference and the x8 geometric self-ensemble are one operation: several network outputs, each a mapped window of the image,
+ * combined into one image by weights.
+ *   img / out : dense [planes][H][W] on the device.   ys[ny], xs[nx], modes[nm] : HOST arrays, copied into the kernel's argument block.
+ *   Window (iy, ix) is the Th x Tw rectangle at (ys[iy], xs[ix]).  View v = (k ny + iy) nx + ix (mode-major, then rows of tiles, then
+ *   columns) is numpy's data_augmentation(window, modes[k]) (util/image_utils.py:133-163: 1 flipud, 2 rot90, 3 rot90 + flipud, 4 rot180,
+ *   5 rot180 + flipud, 6 rot270, 7 rot270 + flipud): [planes][Th][Tw] for modes 0, 1, 4, 5 and [planes][Tw][Th] for 2, 3, 6, 7, dense in
+ *   `views` at planes Th Tw floats per view.
+ *  rcot_view_gather : img -> views.
+ *  rcot_view_blend  : views -> out.  For output pixel (c, y, x), in fp32:
+ *                        num = 0, den = 0
+ *                        for v ascending, if window(v) covers (y, x):  i = y - ys[iy], j = x - xs[ix]
+ *                            w   = wy[i] * wx[j]          (one rounding; wy == wx == NULL: w = 1)
+ *                            a   = the element of view v that the map placed at (i, j)
+ *                            num = num + w * a            (two roundings, no contraction);   den = den + w
+ *                        out = num / den                  (correctly rounded)
+ *                     wy[Th], wx[Tw]: device arrays of positive taps in image orientation, shared by every mode of a window; both NULL
+ *                     or neither.  No atomics, no zero-fill of out, no workspace.  With NULL taps and modes = {0} this is the acc / cnt
+ *                     of averaging overlapping tiles in row-major order, bit for bit.
+ *  RCOT_EINVAL (nothing is launched, the outputs are untouched): a null pointer; planes, ny, nx or nm < 1; a mode outside 0..7 or a
+ *  repeated one; Th or Tw < 4 or no multiple of 4; H or W no multiple of 4; an origin that is no multiple of 4; ys not strictly
+ *  ascending, ys[0] != 0, ys[i+1] - ys[i] > Th or ys[ny-1] + Th != H, and the same for xs (so the windows cover every pixel); img, views,
+ *  out, wy or wx not 16-byte aligned (one float4 form, no scalar twin).  RCOT_EUNSUPPORTED: ny or nx > 64, the argument block's capacity. */
+int rcot_view_gather(const float* img, int planes, int H, int W, const int* ys, int ny, const int* xs, int nx, const int* modes, int nm,
+                     int Th, int Tw, float* views, void* stream);
+int rcot_view_blend(const float* views, int planes, int H, int W, const int* ys, int ny, const int* xs, int nx, const int* modes, int nm,
+                    int Th, int Tw, const float* wy, const float* wx, float* out, void* stream);
 
 #ifdef __cplusplus
 }

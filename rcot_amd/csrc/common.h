@@ -144,6 +144,24 @@ __device__ __forceinline__ void gelu_and_grad(float a, float& g, float& dg) {
     dg = fmaf(a * 0.39894228040143267794f, e, cdf);
 }
 
+// The 8 dihedral maps of numpy's rot90 / flipud composition (the reference's data_augmentation, util/image_utils.py:133-163) on a
+// Th x Tw rectangle: source pixel (sy, sx) of the rectangle for pixel (i, j) of the mapped one.  Modes 0, 1, 4, 5 keep the shape
+// (i < Th, j < Tw); modes 2, 3, 6, 7 give Tw x Th (i < Tw, j < Th).
+__host__ __device__ __forceinline__ void dihedral(int mode, int Th, int Tw, int i, int j, int& sy, int& sx) {
+    switch (mode) {
+        case 1: sy = Th - 1 - i; sx = j; break;              // flipud
+        case 2: sy = j; sx = Tw - 1 - i; break;              // rot90 (counter-clockwise)
+        case 3: sy = j; sx = i; break;                       // rot90 + flipud
+        case 4: sy = Th - 1 - i; sx = Tw - 1 - j; break;     // rot180
+        case 5: sy = i; sx = Tw - 1 - j; break;              // rot180 + flipud
+        case 6: sy = Th - 1 - j; sx = i; break;              // rot270
+        case 7: sy = Th - 1 - j; sx = Tw - 1 - i; break;     // rot270 + flipud
+        default: sy = i; sx = j; break;                      // 0: identity
+    }
+}
+// the mode that undoes `mode` (rot90 and rot270 undo each other; the flips, rot180 and the two transposes undo themselves)
+__host__ __device__ __forceinline__ int dihedral_inverse(int mode) { return mode == 2 ? 6 : mode == 6 ? 2 : mode; }
+
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // "not one of my shapes": what a dispatcher inside the library (dispatch.h) answers so that its caller tries the next kernel

@@ -26,20 +26,6 @@ __device__ __forceinline__ float counter_randn(uint64_t seed, uint64_t idx) {
     return sqrtf(-2.0f * __logf(u1)) * __cosf(6.283185307179586f * u2);
 }
 
-// source pixel (sy, sx) inside the crop for output pixel (i, j) under numpy's rot90 / flipud composition
-__device__ __forceinline__ void dihedral(int mode, int P, int i, int j, int& sy, int& sx) {
-    switch (mode) {
-        case 1: sy = P - 1 - i; sx = j; break;               // flipud
-        case 2: sy = j; sx = P - 1 - i; break;               // rot90 (counter-clockwise)
-        case 3: sy = j; sx = i; break;                       // rot90 + flipud
-        case 4: sy = P - 1 - i; sx = P - 1 - j; break;       // rot180
-        case 5: sy = i; sx = P - 1 - j; break;               // rot180 + flipud
-        case 6: sy = P - 1 - j; sx = i; break;               // rot270
-        case 7: sy = P - 1 - j; sx = P - 1 - i; break;       // rot270 + flipud
-        default: sy = i; sx = j; break;                      // 0: identity
-    }
-}
-
 __global__ __launch_bounds__(256) void patch_prep_kernel(const unsigned char* __restrict__ deg, const unsigned char* __restrict__ clean,
                                                          int W, int y0, int x0, int P, int mode, float sigma, uint64_t seed,
                                                          float* __restrict__ deg_out, float* __restrict__ clean_out) {
@@ -47,7 +33,7 @@ __global__ __launch_bounds__(256) void patch_prep_kernel(const unsigned char* __
     for (int p = blockIdx.x * 256 + threadIdx.x; p < n; p += gridDim.x * 256) {
         const int i = p / P, j = p - i * P;
         int sy, sx;
-        dihedral(mode, P, i, j, sy, sx);
+        rcot::dihedral(mode, P, P, i, j, sy, sx);
         const long src = ((long)(y0 + sy) * W + (x0 + sx)) * 3;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {

@@ -9,7 +9,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 28     # == RCOT_ABI_VERSION in include/rcot_hip.h (checked by tests/test_abi.py and at load time)
+ABI_VERSION = 29     # == RCOT_ABI_VERSION in include/rcot_hip.h (checked by tests/test_abi.py and at load time)
 PREC_FP32, PREC_BF16X3, PREC_BF16X6, PREC_BF16X1 = 0, 1, 2, 3     # RCOT_PREC_* of include/rcot_hip.h
 LIB_PATH = os.environ.get("RCOT_LIB") or os.path.join(_HERE, "librcot_hip.so")   # RCOT_LIB: A/B builds while tuning
 
@@ -122,6 +122,9 @@ SIGNATURES = {
     "rcot_image_egress": [_f, _f, _f, _i, _i, _i, _i, _fl, _f, _f, _f, _f, _sz, _f],
     # standard image-quality figures (csrc/quality.hip)
     "rcot_image_quality": [_f, _f, _i, _i, _i, _i, _f, _f, _sz, _f],
+    # views of an image and their weighted blend: tiles and the x8 self-ensemble (csrc/views.hip)
+    "rcot_view_gather": [_f, _i, _i, _i, _f, _i, _f, _i, _f, _i, _i, _i, _f, _f],             # ys, xs, modes: HOST int arrays
+    "rcot_view_blend": [_f, _i, _i, _i, _f, _i, _f, _i, _f, _i, _i, _i, _f, _f, _f, _f],       # ys, xs, modes: HOST int arrays
 }
 
 _lib = None

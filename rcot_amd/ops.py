@@ -1377,6 +1377,52 @@ class HipBackend:
                                             ws.numel() * ws.element_size(), self._st()), "rcot_image_egress")
         return out_u8, res_u8, stats
 
+    # ------------------------------------------------------------------ views and their blend: tiles, self-ensemble (csrc/views.hip)
+    def _view_args(self, img, ys, xs, modes, Th: int, Tw: int, what: str):
+        self._dense_planes(img, what)
+        H, W = img.shape[-2:]
+        planes = img.numel() // (H * W) if H * W else 0
+        arr = lambda v: (C.c_int * len(v))(*[int(a) for a in v])
+        return planes, H, W, arr(ys), len(ys), arr(xs), len(xs), arr(modes), len(modes), int(Th), int(Tw)
+
+    def view_gather(self, img, ys, xs, modes, Th: int, Tw: int, out=None):
+        """img float [..., H, W] (dense) -> float [len(modes) * len(ys) * len(xs), planes * Th * Tw]: view (k, iy, ix) is the Th x Tw
+        window at (ys[iy], xs[ix]) under the dihedral map modes[k] (numpy's data_augmentation), [planes, Th, Tw] for modes 0, 1, 4, 5 and
+        [planes, Tw, Th] for 2, 3, 6, 7 (rcot_view_gather)"""
+        a = self._view_args(img, ys, xs, modes, Th, Tw, "view_gather")
+        n, per = len(modes) * len(ys) * len(xs), a[0] * int(Th) * int(Tw)
+        if out is None:
+            out = self.empty(n, per)
+        self._dense_planes(out, "view_gather")
+        if out.numel() != n * per:
+            raise _lib.RcotKernelError(f"view_gather: out must hold {n} views of {per} floats")
+        _lib.check(self.L.rcot_view_gather(img.data_ptr(), *a, out.data_ptr(), self._st()), "rcot_view_gather")
+        return out
+
+    def view_blend(self, views, H: int, W: int, ys, xs, modes, Th: int, Tw: int, wy=None, wx=None, out=None):
+        """views as ``view_gather`` lays them out (after the network) -> float [planes, H, W]: every pixel is the mean of the view
+        elements mapped onto it, weighted by wy[i] * wx[j] at window position (i, j) (float [Th] / [Tw] on the device; both None: equal
+        weights), summed in ascending view order (rcot_view_blend)"""
+        self._dense_planes(views, "view_blend")
+        n, vplane = len(modes) * len(ys) * len(xs), int(Th) * int(Tw)
+        if out is None:
+            if n < 1 or vplane < 1 or views.numel() % (n * vplane):
+                raise _lib.RcotKernelError(f"view_blend: views must hold {n} views of whole {Th} x {Tw} planes")
+            out = self.empty(views.numel() // (n * vplane), H, W)
+        self._dense_planes(out, "view_blend")
+        if tuple(out.shape[-2:]) != (H, W):
+            raise _lib.RcotKernelError(f"view_blend: out must be [..., {H}, {W}]")
+        a = self._view_args(out, ys, xs, modes, Th, Tw, "view_blend")
+        if views.numel() != n * a[0] * vplane:
+            raise _lib.RcotKernelError(f"view_blend: views must hold {n} views of {a[0]} planes of {Th} x {Tw}")
+        for t, length in ((wy, Th), (wx, Tw)):
+            if t is not None:
+                self._chk(t, "view_blend")
+                if not t.is_contiguous() or t.numel() != length:
+                    raise _lib.RcotKernelError("view_blend: the taps must be dense float [Th] and [Tw]")
+        _lib.check(self.L.rcot_view_blend(views.data_ptr(), *a, _ptr(wy), _ptr(wx), out.data_ptr(), self._st()), "rcot_view_blend")
+        return out
+
     # ------------------------------------------------------------------ standard image-quality figures (csrc/quality.hip)
     WINDOWS = {"uniform7": 0, "gauss11": 1}
     SPACES = {"rgb": 0, "y": 1}

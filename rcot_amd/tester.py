@@ -1,7 +1,7 @@
 """Whole-image inference behind the CLI of the reference's testers (tester.py, tester_noise.py), on the HIP kernels.
 
     python -m rcot_amd.tester --model checkpoint/model_X__N_S.pth --degset dir/ --tarset dir/ --save OUT/ --savetar TAR/ --saveres RES/
-                              [--noise_sigma 50] [--tile 512 --overlap 32]
+                              [--noise_sigma 50] [--tile 512 --overlap 32] [--tile_window linear --tile_batch 0] [--ensemble 8]
 
 Same walk as the reference (tester.py:56-113, tester_noise.py:65-115): sorted ``glob(degset + "*")`` / ``glob(tarset + "*")`` pairs,
 RGB, [0, 1] floats, pairs of different shapes skipped; ``tester.py`` crops rows / columns from the END until H and W are multiples
@@ -23,6 +23,14 @@ a shape mismatch or when reflect cannot pad it.  ``--metrics device`` takes the 
 Superset: ``--tile T`` processes the image as overlapping T x T tiles (``--overlap`` pixels, averaged where tiles overlap) for sizes
 one does not want to hold whole; the default is the reference's whole-image call.  Restormer takes H, W multiples of 8 (its three
 PixelUnshuffle stages; the reference raises on other sizes), MPRNet multiples of 4.
+
+Superset: ``--tile_window linear|cosine``, ``--tile_batch N`` and ``--ensemble 8`` run the tiles as *views* on the device
+(rcot_amd/tiles.py; csrc/views.hip: rcot_view_gather, rcot_view_blend): the tiles are cut by one kernel, the network takes N of them per
+call (0: all tiles of one shape; tiles of one size are a batch), and one kernel blends them with a separable window that ramps across
+the overlap — the equal-weight average of ``--tile`` alone leaves a step at every overlap border, because neighbouring tiles disagree
+there.  ``--ensemble 8`` is the geometric self-ensemble of restoration tables' "+" rows: the mean of aug^-1(T(aug(x))) over the 8
+dihedral maps of the reference's data_augmentation, per tile, or of the whole image without ``--tile`` (two shapes of four views, one of
+eight for a square image).  With none of the three given, ``--tile`` runs as before, bit for bit.
 
 Superset: ``--ssim_window uniform7|gauss11`` and ``--color y`` report the figures of published tables instead of the reference's own
 (rcot_amd/quality.py): uniform7 = skimage's default structural_similarity (the AirNet / PromptIR protocol, the reference's
@@ -54,6 +62,12 @@ parser.add_argument("--noise_sigma", type=float, default=None, help="tester_nois
 parser.add_argument("--seed", type=int, default=0, help="seed of the added noise")
 parser.add_argument("--tile", type=int, default=0, help="superset: tile size (0 = whole image, the reference's behaviour)")
 parser.add_argument("--overlap", type=int, default=32, help="superset: tile overlap in pixels")
+parser.add_argument("--tile_window", choices=["uniform", "linear", "cosine"], default="uniform",
+                    help="superset: weights of a tile where tiles overlap: uniform = equal (the plain average); linear / cosine = a ramp "
+                         "across the overlap (no step at the overlap borders)")
+parser.add_argument("--tile_batch", type=int, default=1, help="superset: tiles per network call (0 = all tiles of one shape)")
+parser.add_argument("--ensemble", type=int, choices=[1, 8], default=1,
+                    help="superset: 8 = geometric self-ensemble, the mean over the 8 dihedral views (per tile, or of the whole image)")
 parser.add_argument("--pad", choices=["none", "reflect", "replicate"], default="none",
                     help="superset: pad bottom / right to the network's size multiple, restore the whole image, crop back (none = the "
                          "reference's crops and skips)")
@@ -141,13 +155,19 @@ def load_network(path: str):
     return tn, 8
 
 
-def restore(net, x: torch.Tensor, tile: int = 0, overlap: int = 32, mult: int = 8, pad=None) -> torch.Tensor:
+def restore(net, x: torch.Tensor, tile: int = 0, overlap: int = 32, mult: int = 8, pad=None, window: str = "uniform", tile_batch: int = 1,
+            ensemble: int = 1) -> torch.Tensor:
     """``net(x)`` whole (tile 0), or as overlapping tiles averaged where they overlap.  ``pad`` ("reflect" | "replicate"): any H, W —
-    padded to multiples of ``mult`` first, cropped back after (rcot_amd/wholeimage.py)"""
+    padded to multiples of ``mult`` first, cropped back after (rcot_amd/wholeimage.py).  ``window`` ("linear" | "cosine": a ramp across
+    the overlap), ``tile_batch`` (tiles per network call, 0 = all of one shape) or ``ensemble`` (8: the mean over the 8 dihedral views)
+    other than their defaults: the same tiles as views on the device (rcot_amd/tiles.py)"""
     _, _, H, W = x.shape
     if pad not in (None, "none"):
         from .wholeimage import restore_any_size
-        return restore_any_size(net, x, mult, pad, tile, overlap).out[:, :, :H, :W].contiguous()
+        return restore_any_size(net, x, mult, pad, tile, overlap, window, tile_batch, ensemble).out[:, :, :H, :W].contiguous()
+    if (window, tile_batch, ensemble) != ("uniform", 1, 1):
+        from .tiles import plan, restore_views
+        return restore_views(net, x, plan(H, W, tile, overlap, mult, ensemble), window, tile_batch)
     if not tile or (tile >= H and tile >= W):
         return net(x)
     tile = max(mult, tile // mult * mult)
@@ -213,7 +233,7 @@ def _main_any_size(opt, net):
             x = x + torch.from_numpy(rng.normal(size=tar.transpose(2, 0, 1).shape) * opt.noise_sigma / 255.0).float()
         else:
             x = torch.from_numpy(np.ascontiguousarray(deg))
-        r = restore_any_size(net, x, mult, opt.pad, opt.tile, opt.overlap)
+        r = restore_any_size(net, x, mult, opt.pad, opt.tile, opt.overlap, opt.tile_window, opt.tile_batch, opt.ensemble)
         out_u8, res_u8, st = be.image_egress(r.out, h, w, degraded=r.x, target=tar_d, res_scale=3.0 if noisy else 2.0, want_out=True,
                                              want_res=True, want_stats=device_metrics and not standard)
         if device_metrics and standard:
@@ -279,7 +299,7 @@ def main(argv=None):
             x = x + torch.from_numpy(rng.normal(size=tar.transpose(2, 0, 1).shape) * opt.noise_sigma / 255.0).float()
         gt = torch.from_numpy(np.ascontiguousarray(tar.transpose(2, 0, 1))).float().div(255).unsqueeze(0)
         xd = x.cuda()
-        out = restore(net, xd, opt.tile, opt.overlap, mult)
+        out = restore(net, xd, opt.tile, opt.overlap, mult, None, opt.tile_window, opt.tile_batch, opt.ensemble)
         res = (xd - out).cpu()
         save_image(res * (3 if noisy else 2), os.path.join(opt.saveres, name))
         save_image(out.cpu(), os.path.join(opt.save, name))

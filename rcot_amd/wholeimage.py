@@ -47,9 +47,10 @@ def pad_geometry(h: int, w: int, mult: int, mode) -> tuple:
     return Hp, Wp
 
 
-def restore_any_size(net, x_or_u8, mult: int, pad, tile: int = 0, overlap: int = 32) -> Restored:
+def restore_any_size(net, x_or_u8, mult: int, pad, tile: int = 0, overlap: int = 32, window: str = "uniform", tile_batch: int = 1,
+                     ensemble: int = 1) -> Restored:
     """Pad (``pad``: "none" | "reflect" | "replicate"), then ``net`` on the padded image — whole, or as the overlapping tiles of
-    ``tester.restore`` — WITHOUT cropping: rcot_image_egress crops.  ``x_or_u8``: a uint8 [h, w, 3] image (goes through
+    ``tester.restore``, with its ``window`` / ``tile_batch`` / ``ensemble`` — WITHOUT cropping: rcot_image_egress crops.  ``x_or_u8``: a uint8 [h, w, 3] image (goes through
     rcot_image_ingest) or a float [1, 3, h, w] / [3, h, w] tensor (rcot_pad2d); host tensors are copied to the network's device."""
     from .tester import restore
     be = net.be
@@ -63,7 +64,7 @@ def restore_any_size(net, x_or_u8, mult: int, pad, tile: int = 0, overlap: int =
         Hp, Wp = pad_geometry(h, w, mult, pad)
         x = x.reshape(1, 3, h, w).contiguous()
         xp = x if (Hp, Wp) == (h, w) else be.pad2d(x, Hp, Wp, pad)
-    return Restored(restore(net, xp, tile, overlap, mult), xp, h, w, Hp, Wp)
+    return Restored(restore(net, xp, tile, overlap, mult, None, window, tile_batch, ensemble), xp, h, w, Hp, Wp)
 
 
 def image_metrics(stats, h: int, w: int) -> dict:
