@@ -264,6 +264,7 @@ int rcot_ln_stats(const float* x, float* mu, float* rs, int B, int C, int N, voi
    defers that sum: the rcot_ln_bwd_rows(B, C, N) partial rows [rows][2C] stay in ws for rcot_block_param_reduce. */
 int rcot_ln_bwd(const float* g, const float* x, const float* mu, const float* rs, const float* w, const float* dres,
                 float* dx, float* dw, float* db, int B, int C, int N, void* ws, long ws_bytes, void* stream);
+/* (rcot_ln_bwd reads and writes float4 rows: N a multiple of 4 and g, x, mu, rs, dres, dx 16-byte aligned, RCOT_EINVAL otherwise) */
 int rcot_ln_bwd_rows(int B, int C, int N);
 /* Closes the backward of one transformer block in one launch: gw1/gb1 += columns of part1, gw2/gb2 += columns of part2
  * (deferred rcot_ln_bwd partials, same rows and C), gWo += sum_b dWo_part[b], gtemp += sum_b dtemp_part[b], and for
@@ -274,6 +275,8 @@ int rcot_block_param_reduce(const float* part1, const float* part2, int rows, in
                             int heads, const long long* slab_sets, int n_sets, void* stream);
 
 /* ---- depthwise 3x3 stencils (Net_Restormer.py:26, 75-76, 82-83) ------------------------------------------ */
+/* Planes with H and W multiples of 4 run on float4 kernels: every activation / gradient pointer of this group (x, y, p, g, dg, dd,
+ * dp, dy, dx, dd_scratch; not the weights) must then be 16-byte aligned, RCOT_EINVAL otherwise. */
 /* y = dwconv3x3(x, w[C][3][3], pad 1); flip=1 correlates with the rotated filter (= data gradient). */
 int rcot_dwconv3x3(const float* x, const float* w, float* y, int B, int C, int H, int W, int flip, void* stream);
 /* g[b][j] = gelu_erf(dw(p)[b][j]) * dw(p)[b][j+hid]   (p has 2*hid channels)  — Net_Restormer.py:82-83 */
@@ -295,7 +298,8 @@ int rcot_dwconv3x3_bwd(const float* dy, const float* x, const float* w, float* d
                        void* stream);
 
 /* ---- MDTA small-matrix core (Net_Restormer.py:39-43) -------------------------------------- */
-/* out[b*R + r] = sum_n x[b*sXb + r*N + n]^2   (|q|^2, |k|^2 rows for F.normalize, :39-40) */
+/* out[b*R + r] = sum_n x[b*sXb + r*N + n]^2   (|q|^2, |k|^2 rows for F.normalize, :39-40); float4 loads: N and sXb multiples of
+ * 4, x 16-byte aligned (RCOT_EINVAL otherwise) */
 int rcot_row_sumsq(const float* x, float* out, int B, int R, int N, long sXb, void* stream);
 /* Gn = Graw/(nq nk^T); A = softmax_rows(tau*Gn)  (Net_Restormer.py:39-43).  c = C/heads <= 96.
  * The fold Mf[b] = W_o * blockdiag_h(A[b,h]) is an rcot_bmm_nn call over (image, head). */

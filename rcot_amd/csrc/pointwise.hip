@@ -1254,7 +1254,7 @@ int rcot_ln_bwd(const float* g, const float* x, const float* mu, const float* rs
                 float* dx, float* dw, float* db, int B, int C, int N, void* ws, long ws_bytes, void* stream) {
     if (!g || !x || !mu || !rs || !w || !dx || !ws || B <= 0 || C <= 0 || C > 512 || N <= 0 || B > 65535) return RCOT_EINVAL;
     if ((dw == nullptr) != (db == nullptr)) return RCOT_EINVAL;   // both null: the partial rows stay in ws (deferred reduce)
-    if (N & 3) return RCOT_EINVAL;
+    if ((N & 3) || !al16(g) || !al16(x) || !al16(mu) || !al16(rs) || !al16(dx) || !al16(dres)) return RCOT_EINVAL;   // float4 rows
     // 64-pixel tiles while they still give >= 512 workgroups, 16-pixel tiles on the small levels; at most ~1024 partial rows
     const bool wide = (long)cdiv(N, 64) * B >= 512;
     const int tiles = cdiv(N, wide ? 64 : 16);
@@ -1336,6 +1336,7 @@ int rcot_dwconv3x3(const float* x, const float* w, float* y, int B, int C, int H
         RCOT_LAUNCH_CHECK();
         return RCOT_OK;
     }
+    if (!al16(x) || !al16(y)) return RCOT_EINVAL;          // the quad kernels load and store float4
     const long nq = (long)B * C * (H >> 2) * (W >> 2);
     const bool nb = nb_lanes_ok(W);
 #define RCOT_DW(F, NB_) do { note_kernel("dwconv_kernel<%s, %s>", tf(F), tf(NB_)); RCOT_LAUNCH((dwconv_kernel<F, NB_>), dim3(cdiv(nq, 256)), dim3(256), 0, (hipStream_t)stream, x, w, y, nq, C, H, W); } while (0)
@@ -1354,6 +1355,7 @@ int rcot_gdfn_gate_fwd(const float* p, const float* w, float* g, int B, int hid,
         RCOT_LAUNCH_CHECK();
         return RCOT_OK;
     }
+    if (!al16(p) || !al16(g)) return RCOT_EINVAL;
     const long nq = (long)B * hid * (H >> 2) * (W >> 2);
     // the neighbour-lane form of the patch loads (all twelve rows of both planes requested before the first lane shift; with the
     // loads inside per-row `if` blocks it measured SLOWER than the scalar-halo form, 33.8 vs 30.8 us)
@@ -1368,6 +1370,7 @@ int rcot_gdfn_gate_fwd(const float* p, const float* w, float* g, int B, int hid,
 int rcot_gdfn_gate_bwd(const float* p, const float* w, const float* dg, float* dd, float* dwg, int B, int hid, int H,
                        int W, void* stream) {
     if (!p || !w || !dg || !dd || B <= 0 || hid <= 0 || H <= 0 || W <= 0 || (W & 3) || (H & 3)) return RCOT_EINVAL;
+    if (!al16(p) || !al16(dg) || !al16(dd)) return RCOT_EINVAL;
     // strip height: the tallest of 16 / 8 / 4 rows that still leaves >= 400k threads (about 6 wavefronts per SIMD)
     const long cols = (long)B * hid * (W >> 2);
     bool fused = true;
@@ -1382,6 +1385,7 @@ int rcot_gdfn_gate_bwd(const float* p, const float* w, const float* dg, float* d
 
 int rcot_dwconv3x3_wgrad(const float* dy, const float* x, float* dw, int B, int C, int H, int W, void* stream) {
     if (!dy || !x || !dw || B <= 0 || C <= 0 || H <= 0 || W <= 0 || (W & 3) || (H & 3) || B > 65535) return RCOT_EINVAL;
+    if (!al16(dy) || !al16(x)) return RCOT_EINVAL;
     const long planes = (long)B * C;
     const int nb4 = (H >> 2) * (W >> 2);
     if (nb4 <= 16)
@@ -1397,6 +1401,7 @@ int rcot_dwconv3x3_wgrad(const float* dy, const float* x, float* dw, int B, int 
 int rcot_gdfn_bwd(const float* p, const float* w, const float* dg, float* dp, float* dwg, float* dd_scratch, int B, int hid,
                   int H, int W, void* stream) {
     if (!p || !w || !dg || !dp || !dwg || B <= 0 || hid <= 0 || H <= 0 || W <= 0 || (W & 3) || (H & 3)) return RCOT_EINVAL;
+    if (!al16(p) || !al16(dg) || !al16(dp) || !al16(dd_scratch)) return RCOT_EINVAL;
     const int wq = W >> 2;
     bool fused = wq <= 64 && (64 % wq) == 0;                  // the neighbour-lane exchange needs whole row segments per wavefront
     if (fused) {
@@ -1419,6 +1424,7 @@ int rcot_dwconv3x3_bwd(const float* dy, const float* x, const float* w, float* d
                        void* stream) {
     if (!dy || !x || !w || !dx || !dwg || B <= 0 || C <= 0 || H <= 0 || W <= 0 || (W & 3) || (H & 3) || B > 65535)
         return RCOT_EINVAL;
+    if (!al16(dy) || !al16(x) || !al16(dx)) return RCOT_EINVAL;
     const long cols = (long)B * C * (W >> 2);
     bool fused = true;
     int rc;
@@ -1435,7 +1441,7 @@ int rcot_dwconv3x3_bwd(const float* dy, const float* x, const float* w, float* d
 }
 
 int rcot_row_sumsq(const float* x, float* out, int B, int R, int N, long sXb, void* stream) {
-    if (!x || !out || B <= 0 || R <= 0 || N <= 0 || (N & 3) || (sXb & 3) || B > 65535) return RCOT_EINVAL;
+    if (!x || !out || B <= 0 || R <= 0 || N <= 0 || (N & 3) || (sXb & 3) || !al16(x) || B > 65535) return RCOT_EINVAL;
     RCOT_LAUNCH(row_sumsq_kernel, dim3(R, B), dim3(256), 0, (hipStream_t)stream, x, out, R, N, sXb);
     RCOT_LAUNCH_CHECK();
     return RCOT_OK;

@@ -3,6 +3,9 @@ independent fp64 CPU statement of the same operation (tests/host_double.py, itse
 oracle by the CPU tier).  Shapes are the ones the transport map / critic actually use (odd hidden sizes
 127/255/510/1021, heads 1/2/4/8, 24/48/96 channels per head, k5s1/k4s2/k3s1 convs).
 Tolerance: fp32 rounding only (the MFMA path is an exact fp32 fmaf chain): 2e-5 relative to max|ref|.
+Every device tensor comes from a GuardSet (tests/guarded.py: NaN-patterned bands of 16 KiB on either side, checked bit for bit at the
+end of the test) and the backend's workspaces hold NaN before the kernels run: a write outside an output, a read outside an input and
+a read of workspace nobody filled all fail here.
 """
 import os
 
@@ -11,6 +14,7 @@ import pytest
 import torch
 
 from conftest import relerr, seeded_tensor
+from guarded import GuardSet, all_finite, poison_workspaces
 from host_double import TorchDouble
 
 pytestmark = pytest.mark.gpu
@@ -36,13 +40,19 @@ def both(hip, fn, arrays, outs, tol=TOL):
     if getattr(hip, "prec", 0) == 1:
         tol = max(tol, X3_TOL)
     cpu = [None if a is None else a.double().clone() for a in arrays]
-    gpu = [None if a is None else a.cuda() for a in arrays]
+    gs = GuardSet("cuda")
+    gpu = [None if a is None else gs.tensor(a, f"arrays[{i}]") for i, a in enumerate(arrays)]
     fn(DBL, *cpu)
+    poison_workspaces(hip)
     fn(hip, *gpu)
     torch.cuda.synchronize()
     for i in outs:
         e = relerr(gpu[i], cpu[i])
         assert e < tol, (i, e)
+    for i in outs:
+        assert all_finite(gpu[i]), i
+    gs.check()
+    return cpu, gpu
 
 
 # ----------------------------------------------------------------------------- 1x1 projections
@@ -182,7 +192,9 @@ def test_kmajor_multi_equals_three_launches(hip, B, heads, c, N):
     bit-identical to its own rcot_gemm_kmajor launch (all three tile shapes), and the launch really is one kernel."""
     import ctypes
     be, C = hip, heads * c
-    g = lambda seed, *sh: seeded_tensor(seed, sh).cuda()
+    gs = GuardSet("cuda")
+    poison_workspaces(be)
+    g = lambda seed, *sh: gs.tensor(seeded_tensor(seed, sh))
     u, dy = g(1, B, 3 * C, N), g(2, B, C, N)
     Mf, Eq, EqT = g(3, B, C, C), g(4, B, heads, c, c), g(5, B, heads, c, c)
     Dq, Dk = g(6, B, C), g(7, B, C)
@@ -191,7 +203,7 @@ def test_kmajor_multi_equals_three_launches(hip, B, heads, c, N):
     dy4 = dy.view(B, 1, C, N)
     outs = []
     for multi in (True, False):
-        du = torch.full((B, 3 * C, N), float("nan"), device="cuda")
+        du = gs.full((B, 3 * C, N), float("nan"), name=f"du multi={multi}")
         dd = du.view(B, 3, heads, c, N)
         dQ, dK, dV = dd[:, 0], dd[:, 1], du.view(B, 3, C, N)[:, 2].unsqueeze(1)
         if multi:
@@ -209,6 +221,7 @@ def test_kmajor_multi_equals_three_launches(hip, B, heads, c, N):
     assert torch.equal(outs[0], outs[1])
     ref = torch.einsum("bkm,bkn->bmn", Mf.double().cpu(), dy.double().cpu())
     assert relerr(outs[0].view(B, 3, C, N)[:, 2], ref) < TOL
+    gs.check()
 
 
 @pytest.mark.parametrize("Z,M,K,N,res", [(2, 96, 96, 1024, True), (8, 48, 127, 16384, True), (3, 96, 255, 128, True), (2, 48, 48, 4096, False),
@@ -244,14 +257,18 @@ def test_kgroup_kernel_odd_slab_counts_and_ragged_rows(hip, Z, M, K, N):
         At = torch.zeros(Z, 1, rows, ld)
         At[:, 0, :K, :M] = A.transpose(1, 2)
         Bm, R = seeded_tensor(2, (Z, 1, K, N)), seeded_tensor(3, (Z, 1, M, N))
-        Cc = torch.full((Z, 1, M, N), float("nan")).cuda()
-        be.gemm_kmajor(At.cuda(), Bm.cuda(), Cc, M, K, R=R.cuda())
+        gs = GuardSet("cuda")
+        poison_workspaces(be)
+        Cc = gs.full((Z, 1, M, N), float("nan"), name="C")
+        # At: a_rows = ceil16(K) rows, readable and zero past K (include/rcot_hip.h, rcot_gemm_kmajor), built so inside the guarded tensor
+        be.gemm_kmajor(gs.tensor(At, "At"), gs.tensor(Bm, "B"), Cc, M, K, R=gs.tensor(R, "R"))
         buf = ctypes.create_string_buffer(192)
         be.L.rcot_last_kernel(buf, 192)
         assert buf.value.decode() == "gemm_xx_kg_kernel", buf.value
         torch.cuda.synchronize()
         ref = A.double() @ Bm[:, 0].double() + R[:, 0].double()
         assert relerr(Cc[:, 0], ref) < TOL
+        gs.check()
     finally:
         be.prec = p0
 
@@ -262,28 +279,31 @@ def test_attn_core_bwd_takes_dM_as_slabs(hip, B, heads, c, N):
     the schedule hands over the dense tensor: the slab route saved a launch and no time) against the dense form: same results up to
     the order of the slab sum."""
     be, C = hip, heads * c
-    g = lambda seed, *sh, **kw: seeded_tensor(seed, sh, **kw).cuda()
+    gs = GuardSet("cuda")
+    poison_workspaces(be)
+    g = lambda seed, *sh, **kw: gs.tensor(seeded_tensor(seed, sh, **kw))
     dy, V = g(1, B, 1, C, N), g(2, B, 1, C, N)
-    Wo, temp = g(3, C, C, scale=0.1), 1 + 0.2 * g(4, heads)
-    Gn = torch.tanh(g(5, B, heads, c, c))
-    A = torch.softmax(Gn * temp.view(1, heads, 1, 1), -1).contiguous()
-    sq = 1 + g(6, B, 2 * C).abs()
+    Wo, temp = g(3, C, C, scale=0.1), gs.tensor(1 + 0.2 * g(4, heads))
+    Gn = gs.tensor(torch.tanh(g(5, B, heads, c, c)))
+    A = gs.tensor(torch.softmax(Gn * temp.view(1, heads, 1, 1), -1))
+    sq = gs.tensor(1 + g(6, B, 2 * C).abs())
     res = []
     for slabs in (True, False):
-        outs = [torch.full(sh, float("nan"), device="cuda") for sh in ((B, C, C), (B, C, C), (B, heads), (B, heads, c, c), (B, heads, c, c), (B, C), (B, C))]
+        outs = [gs.full(sh, float("nan")) for sh in ((B, C, C), (B, C, C), (B, heads), (B, heads, c, c), (B, heads, c, c), (B, C), (B, C))]
         if slabs:
             d = be.bmm_nt_slabs(dy, V)
             assert isinstance(d, tuple) and d[1] >= 1, d
             if d[1] > 8:
                 pytest.skip(f"split factor {d[1]} > 8 on this shape")
         else:
-            d = torch.empty(B, C, C, device="cuda")
+            d = gs.empty((B, C, C), name="dM dense")
             be.bmm_nt(dy, V, d.unsqueeze(1))
         assert be.attn_core_bwd(d, Wo, A, Gn, sq, temp, *outs)
         torch.cuda.synchronize()
         res.append(outs)
     for a, b in zip(*res):
         assert relerr(a, b) < 1e-5
+    gs.check()
 
 
 @pytest.mark.parametrize("B,heads,c", [(2, 1, 48), (2, 2, 48), (8, 8, 48), (2, 1, 96), (1, 4, 96), (3, 2, 96), (2, 4, 24), (8, 4, 48)])
@@ -329,6 +349,15 @@ def test_row_sumsq(hip):
     both(hip, fn, [T(1, B, 3 * C, N), torch.zeros(B, 2 * C)], [1])
 
 
+# N: below one sweep of 256 float4 lanes, a ragged sweep, exactly one, one plus a quad, four; on a channel slice (sXb > R * N)
+@pytest.mark.parametrize("R", [1, 96])
+@pytest.mark.parametrize("N", [4, 260, 1024, 1028, 4096])
+def test_row_sumsq_sweeps(hip, N, R):
+    def fn(be, u, out):
+        be.row_sumsq(u[:, :R], out)
+    both(hip, fn, [T(1, 2, R + 3, N), torch.zeros(2, R)], [1])
+
+
 # ----------------------------------------------------------------------------- LayerNorm / stencils
 @pytest.mark.parametrize("B,C,H,W", [(2, 48, 16, 16), (1, 96, 32, 64), (2, 384, 8, 8), (1, 192, 24, 40)])
 def test_layernorm(hip, B, C, H, W):
@@ -349,6 +378,17 @@ def test_dwconv(hip, B, C, H, W):
         be.dwconv3x3_wgrad(dy, x, dw)
     both(hip, fn, [T(1, B, C, H, W), T(2, C, 9), torch.zeros(B, C, H, W), torch.zeros(B, C, H, W), T(3, B, C, H, W), T(4, C, 9)],
          [2, 3, 5])
+
+
+# planes with a side that is no multiple of 4 (whole images padded to multiples of 8 give 5 x 6 and 10 x 12 at the lower levels):
+# dwconv_any_kernel and gate_fwd_any_kernel, one thread per output, every tap clamped on its own; the last plane's bottom row is
+# followed by the rear band; (3, 7, 343, 343): a second trip of the grid-stride loop
+@pytest.mark.parametrize("B,hid,H,W", [(2, 3, 5, 6), (1, 2, 10, 12), (1, 5, 7, 9), (2, 1, 1, 1), (3, 7, 343, 343)])
+def test_stencils_at_any_plane_size(hip, B, hid, H, W):
+    def fn(be, x, w, y, g):
+        be.dwconv3x3(x, w, y)
+        be.gdfn_gate_fwd(x, w, g)
+    both(hip, fn, [T(1, B, 2 * hid, H, W), T(2, 2 * hid, 9, scale=0.5), torch.zeros(B, 2 * hid, H, W), torch.zeros(B, hid, H, W)], [2, 3])
 
 
 @pytest.mark.parametrize("B,C,N,heads", [(2, 96, 4096, 1), (8, 48, 16384, 1), (2, 192, 1024, 4), (3, 384, 256, 8)])
@@ -471,14 +511,17 @@ def test_conv_pcm(hip, B, Ci, Co, H, W, k):
     dZ = T(4, B, Co, Ho, Wo)
     ref = F.leaky_relu(F.conv2d(X.double(), Wt.double(), bias.double(), s, 1), 0.2)
     ref_dx = torch.nn.grad.conv2d_input(X.shape, Wt.double(), dZ.double(), s, 1)
-    Wg = Wt.cuda()
+    gs = GuardSet("cuda")
+    poison_workspaces(hip)
+    Wg = gs.tensor(Wt, "W")
     pf, pd = hip.conv_pcm_pack(Wg, "fwd"), hip.conv_pcm_pack(Wg, "dgrad")
-    Y, dX = torch.full((B, Co, Ho, Wo), float("nan"), device="cuda"), torch.full((B, Ci, H, W), float("nan"), device="cuda")
-    hip.conv_pcm_fwd(X.cuda(), pf, bias.cuda(), Y, k, lrelu=0.2)
-    hip.conv_pcm_dgrad(dZ.cuda(), pd, dX, k)
+    Y, dX = gs.full((B, Co, Ho, Wo), float("nan"), name="Y"), gs.full((B, Ci, H, W), float("nan"), name="dX")
+    hip.conv_pcm_fwd(gs.tensor(X, "X"), pf, gs.tensor(bias, "bias"), Y, k, lrelu=0.2)
+    hip.conv_pcm_dgrad(gs.tensor(dZ, "dZ"), pd, dX, k)
     torch.cuda.synchronize()
     e1, e2 = relerr(Y, ref), relerr(dX, ref_dx)
     assert e1 < X3_TOL and e2 < X3_TOL, (e1, e2)
+    gs.check()
 
 
 @pytest.mark.parametrize("B,Ci,Co,H,W", [(2, 96, 192, 64, 64), (8, 384, 768, 16, 16), (3, 192, 96, 32, 16), (2, 96, 48, 64, 64), (1, 48, 64, 20, 24)])
@@ -494,17 +537,20 @@ def test_conv_pcm_wgrad(hip, B, Ci, Co, H, W, x3):
     ref_dx = torch.nn.grad.conv2d_input(X.shape, Wt.double(), dZ.double(), 1, 1)
     old = hip.prec
     hip.prec = lib.PREC_BF16X3 if x3 else lib.PREC_FP32
+    gs = GuardSet("cuda")
+    poison_workspaces(hip)
     try:
-        dW = W0.cuda().clone()
-        ok = hip.conv_pcm_wgrad(dZ.cuda(), X.cuda(), dW, 1.0)
+        dW, dZg = gs.tensor(W0, "dW"), gs.tensor(dZ, "dZ")
+        ok = hip.conv_pcm_wgrad(dZg, gs.tensor(X, "X"), dW, 1.0)
         assert ok
-        dX = torch.full((B, Ci, H, W), float("nan"), device="cuda")
-        hip.conv_pcm_dgrad(dZ.cuda(), hip.conv_pcm_pack(Wt.cuda(), "dgrad"), dX, 3, prepped=True)
+        dX = gs.full((B, Ci, H, W), float("nan"), name="dX")
+        hip.conv_pcm_dgrad(dZg, hip.conv_pcm_pack(gs.tensor(Wt, "W"), "dgrad"), dX, 3, prepped=True)
         torch.cuda.synchronize()
     finally:
         hip.prec = old
     e, e2 = relerr(dW, ref), relerr(dX, ref_dx)
     assert e < (X3_TOL if x3 else TOL) and e2 < X3_TOL, (e, e2)
+    gs.check()
 
 
 @pytest.mark.parametrize("cmap", [1, 2])
@@ -531,8 +577,10 @@ def test_linear(hip, B, i, o):
 
 
 # ----------------------------------------------------------------------------- elementwise / critic pieces
-def test_elementwise(hip):
-    B, C, H, W = 3, 8, 16, 16
+# (2, 3, 5, 7): nothing divisible by 4, P < 256 for bias_grad; (2, 9, 343, 343): 2 117 682 elements, above the 8192 x 256 threads of
+# grid_for, so every grid-stride loop takes a second trip
+@pytest.mark.parametrize("B,C,H,W", [(3, 8, 16, 16), (2, 3, 5, 7), (1, 1, 1, 1), (2, 9, 343, 343)])
+def test_elementwise(hip, B, C, H, W):
 
     def fn(be, x, y, o1, cat, a, dz, db, al, lo, norms, u0, gp):
         be.axpby(x, y, o1, 1.0, -0.8)
@@ -549,14 +597,70 @@ def test_elementwise(hip):
     both(hip, fn, arrs, [0, 2, 3, 5, 6, 8, 9, 10, 11])
 
 
+def test_gp_penalty_with_a_zero_gradient(hip):
+    """one sample's gradient is exactly zero: its u0 must be exactly zero (the kernel's nm > 0 branch), and gp / u0 are the value and
+    the torch.autograd gradient of 10/Bg * sum_b (|g_b| - 1)^2 in fp64 (host_double.gp_penalty divides by the norm: NaN there)"""
+    B, inv = 3, 1.0 / 6
+
+    def fn(be, g, norms, u0, gp):
+        if be is hip:
+            be.gp_penalty(g, norms, u0, gp, inv)
+            return
+        x = g.clone().requires_grad_(True)
+        n = torch.linalg.vector_norm(x.reshape(B, -1), dim=1)
+        val = 10.0 * inv * ((n - 1) ** 2).sum()
+        u0.copy_(torch.autograd.grad(val, x)[0])
+        norms.copy_(n.detach())
+        gp.fill_(float(val.detach()))
+    g = T(1, B, 2, 5, 7)
+    g[1] = 0.0
+    cpu, gpu = both(hip, fn, [g, torch.zeros(B), torch.zeros(B, 2, 5, 7), torch.zeros(1)], [1, 2, 3])
+    assert bool((cpu[2][1] == 0).all()) and bool((gpu[2][1] == 0).all()) and float(gpu[1][1]) == 0.0
+
+
+# unaligned head and tail of fill_kernel: lengths around the float4 width, one that fills no quad, 1023, and one above the
+# 4 x 8192 x 256 floats of one trip; exactly [off, off + n) changes, the bands prove the rest
+@pytest.mark.parametrize("off", [0, 1, 2, 3])
+@pytest.mark.parametrize("n", [1, 3, 4, 5, 1023, 2097157])
+def test_fill_head_and_tail(hip, n, off):
+    gs = GuardSet("cuda")
+    t = gs.full((off + n + 3,), -7.0, name="t")
+    hip.fill(t[off:off + n], 2.5)
+    torch.cuda.synchronize()
+    want = torch.full((off + n + 3,), -7.0)
+    want[off:off + n] = 2.5
+    assert torch.equal(t.cpu(), want)
+    gs.check()
+
+
+@pytest.mark.parametrize("planes,H,W", [(4, 2, 2), (12, 6, 10), (8, 24, 40)])
+@pytest.mark.parametrize("mode", [1, 2])
+def test_pixel_shuffle(hip, mode, planes, H, W):
+    """both maps against F.pixel_unshuffle / F.pixel_shuffle (host_double), exact: the kernel only moves floats"""
+    oshape = (1, 4 * planes, H // 2, W // 2) if mode == 1 else (1, planes // 4, 2 * H, 2 * W)
+
+    def fn(be, x, y):
+        be.pixel_shuffle(x, y, mode)
+    cpu, gpu = both(hip, fn, [T(1, 1, planes, H, W), torch.zeros(*oshape)], [1])
+    assert torch.equal(gpu[1].cpu(), cpu[1].float())
+
+
+@pytest.mark.parametrize("beta", [0.0, 1.0])
+@pytest.mark.parametrize("n", [1, 5, 4099])
+@pytest.mark.parametrize("B", [1, 3, 8])
+def test_batch_reduce(hip, B, n, beta):
+    def fn(be, src, dst):
+        be.batch_reduce(src, dst, beta=beta)
+    both(hip, fn, [T(1, B, n), T(2, n)], [1])
+
+
 # ----------------------------------------------------------------------------- OT cost
 @pytest.mark.parametrize("P_,paired", [(32, False), (64, True), (128, True)])
 def test_ot_cost(hip, P_, paired):
     B = 4
     de = [0, 2, 3, 7]
 
-    def fn(be, deg, out, tgt, dout, sums, spec, scal, gF):
-        d = torch.tensor(de, dtype=torch.int32, device=deg.device)
+    def fn(be, d, deg, out, tgt, dout, sums, spec, scal, gF):
         be.ot_reduce(deg, out, tgt if paired else None, sums)
         be.ot_spectrum(deg, out, d, gF, spec)
         be.ot_grad(deg, out, tgt if paired else None, d, gF, sums, spec, dout, scal, 1.0, 10000.0, B)
@@ -566,10 +670,13 @@ def test_ot_cost(hip, P_, paired):
     arrs = [deg, out, T(3, B, 3, P_, P_, scale=0.3), T(4, B, 3, P_, P_, scale=0.01), torch.zeros(2 * B + 2), torch.zeros(B),
             torch.zeros(3), torch.zeros(B, 3, P_, P_)]
     cpu = [a.double().clone() for a in arrs]
-    gpu = [a.cuda() for a in arrs]
-    fn(DBL, *cpu)
-    fn(hip, *gpu)
+    gs = GuardSet("cuda")
+    gpu = [gs.tensor(a, f"arrs[{i}]") for i, a in enumerate(arrs)]
+    fn(DBL, torch.tensor(de, dtype=torch.int32), *cpu)
+    poison_workspaces(hip)
+    fn(hip, gs.tensor(torch.tensor(de, dtype=torch.int32), "de_id"), *gpu)
     torch.cuda.synchronize()
+    gs.check()
     assert relerr(gpu[4], cpu[4]) < 1e-5 and relerr(gpu[6], cpu[6]) < 1e-5
     assert relerr(gpu[5][2:], cpu[5][2:]) < 1e-5
     # gradient: the |F|=0 / single-bin planes are degenerate for F/|F| in fp32 (tiny bins flip phase); compare the rest
@@ -583,11 +690,15 @@ def test_ot_cost(hip, P_, paired):
 def test_ot_cost_golden(hip, gold):
     """The trainer's inline expression evaluated by the REFERENCE (fixture otcost.npz)."""
     fx = gold("otcost.npz")
-    res = torch.from_numpy(fx["res"]).cuda()
+    gs = GuardSet("cuda")
+    poison_workspaces(hip)
+    res = torch.from_numpy(fx["res"])
     B = res.shape[0]
-    de = torch.tensor(fx["de_id"], dtype=torch.int32).cuda()
-    deg, out = res.clone(), torch.zeros_like(res)
-    sums, spec, scal, gF, dout = hip.empty(2 * B + 2), hip.empty(B), hip.empty(3), hip.empty(*res.shape), hip.zeros(*res.shape)
+    de = gs.tensor(torch.tensor(fx["de_id"], dtype=torch.int32), "de_id")
+    deg, out = gs.tensor(res, "deg"), gs.full(res.shape, 0.0, name="out")
+    sums, spec, scal, gF = gs.empty((2 * B + 2,), name="sums"), gs.empty((B,), name="spec"), gs.empty((3,), name="scal"), gs.empty(res.shape, name="gF")
+    dout = gs.empty(res.shape, name="dout")
+    hip.fill(dout, 0.0)
     hip.ot_reduce(deg, out, None, sums)
     hip.ot_spectrum(deg, out, de, gF, spec)
     hip.ot_grad(deg, out, None, de, gF, sums, spec, dout, scal, 1.0, 0.0, B)
@@ -599,19 +710,21 @@ def test_ot_cost_golden(hip, gold):
     m[1, 0] = 0
     m[3, 1] = 0
     assert relerr(-dout.cpu() * m, torch.from_numpy(fx["dres"]) * m) < 5e-5
+    gs.check()
 
 
 # ----------------------------------------------------------------------------- optimizers
-def test_optimizers(hip):
-    n = 64 * 1000
-
+# n = 4 194 308: one float4 past 4096 x 256 x 4, the grid cap of csrc/optim.hip
+@pytest.mark.parametrize("grad_scale", [1.0, 0.5])
+@pytest.mark.parametrize("n", [4, 4004, 64000, 4194308])
+def test_optimizers(hip, n, grad_scale):
     def fn(be, p, g, sq, p2, m, v):
         for _ in range(3):
-            be.rmsprop_step(p, g, sq, n, 1e-3)
+            be.rmsprop_step(p, g, sq, n, 1e-3, grad_scale=grad_scale)
         for t in range(1, 4):
-            be.adam_step(p2, g, m, v, n, 1e-3, t)
+            be.adam_step(p2, g, m, v, n, 1e-3, t, grad_scale=grad_scale)
     g = T(2, n)
-    g[:100] = 0.0
+    g[:min(100, n // 2)] = 0.0
     both(hip, fn, [T(1, n), g, torch.zeros(n), T(3, n), torch.zeros(n), torch.zeros(n)], [0, 2, 3, 4, 5], tol=1e-5)
 
 
@@ -664,15 +777,17 @@ def test_fp32_ln_statistics_made_by_the_projection(hip, B, Ci, Co, N, ratio):
     mu = Xd.mean(1, keepdim=True)
     rstd = (Xd.var(1, unbiased=False, keepdim=True) + 1e-5).rsqrt()
     ref = R.double() + torch.einsum("oc,bcn->bon", W.double(), (Xd - mu) * rstd * lw.double().view(1, Ci, 1) + lb.double().view(1, Ci, 1))
-    g = lambda t: t.cuda()
+    gs = GuardSet("cuda")
+    poison_workspaces(be)
+    g = lambda t: gs.tensor(t)
     Wg, Xg, Rg, lwg, lbg = g(W), g(X), g(R), g(lw), g(lb)
-    WT, WP = (torch.zeros(*s, device="cuda") for s in be.pack_shapes(Co, Ci))
-    WTf, c12 = (torch.zeros(*s, device="cuda") for s in be.fold_shapes(Co, Ci))
+    WT, WP = (gs.full(s, 0.0) for s in be.pack_shapes(Co, Ci))
+    WTf, c12 = (gs.full(s, 0.0) for s in be.fold_shapes(Co, Ci))
     be.pack_weight(Wg, WT, WP, (lwg, lbg, WTf, c12))
     outs = []
     for fused in (True, False):
-        mu_, rs_ = torch.full((B, N), float("nan"), device="cuda"), torch.full((B, N), float("nan"), device="cuda")
-        Y = torch.full((B, Co, N), float("nan"), device="cuda")
+        mu_, rs_ = gs.full((B, N), float("nan")), gs.full((B, N), float("nan"))
+        Y = gs.full((B, Co, N), float("nan"))
         calls = []
         orig, be.ln_fused = be.ln_stats, fused
         be.ln_stats = lambda *a: (calls.append(1), orig(*a))
@@ -690,6 +805,7 @@ def test_fp32_ln_statistics_made_by_the_projection(hip, B, Ci, Co, N, ratio):
     e_mu = float((m1.double().cpu() - mu[:, 0]).abs().max() / mu.abs().max())
     e_rs = float((r1.double().cpu() / rstd[:, 0] - 1).abs().max())
     assert e_mu < 2e-6 and e_rs < 2e-5 * (1 + ratio) and relerr(Y1, ref) < TOL * (1 + ratio)
+    gs.check()
 
 
 @pytest.mark.parametrize("B,Ci,Co,N,ln,res", [(8, 96, 288, 16384, True, False), (8, 255, 96, 16384, False, True), (3, 100, 330, 16384, True, True)])
@@ -701,20 +817,22 @@ def test_streaming_tile_stores_change_no_bit(hip, B, Ci, Co, N, ln, res):
     from rcot_amd import lib
     be = hip
     assert be.prec == lib.PREC_FP32
-    g = lambda t: t.cuda()
+    gs = GuardSet("cuda")
+    poison_workspaces(be)
+    g = lambda t: gs.tensor(t)
     Wg, Xg, Rg = g(seeded_tensor(1, (Co, Ci), scale=0.1)), g(seeded_tensor(2, (B, Ci, N))), g(seeded_tensor(5, (B, Co, N)))
     lwg, lbg = g(1 + 0.1 * seeded_tensor(3, (Ci,))), g(0.1 * seeded_tensor(4, (Ci,)))
-    WT, WP = (torch.zeros(*s, device="cuda") for s in be.pack_shapes(Co, Ci))
-    WTf, c12 = (torch.zeros(*s, device="cuda") for s in be.fold_shapes(Co, Ci))
+    WT, WP = (gs.full(s, 0.0) for s in be.pack_shapes(Co, Ci))
+    WTf, c12 = (gs.full(s, 0.0) for s in be.fold_shapes(Co, Ci))
     be.pack_weight(Wg, WT, WP, (lwg, lbg, WTf, c12))
-    mu_, rs_ = torch.empty(B, N, device="cuda"), torch.empty(B, N, device="cuda")
+    mu_, rs_ = gs.empty((B, N)), gs.empty((B, N))
     be.ln_stats(Xg, mu_, rs_)
     outs = []
     old = os.environ.get("RCOT_XX_NTS_MB")
     try:
         for mb in ("32", "0"):
             os.environ["RCOT_XX_NTS_MB"] = mb
-            Y = torch.full((B, Co, N), float("nan"), device="cuda")
+            Y = gs.full((B, Co, N), float("nan"), name=f"Y nts={mb}")
             be.conv1x1_fwd(Wg, Xg, Y, ln=(mu_, rs_, lwg, lbg) if ln else None, R=Rg if res else None, packed=(WT, WP, (WTf, c12)))
             torch.cuda.synchronize()
             outs.append(Y)
@@ -724,6 +842,7 @@ def test_streaming_tile_stores_change_no_bit(hip, B, Ci, Co, N, ln, res):
         else:
             os.environ["RCOT_XX_NTS_MB"] = old
     assert torch.equal(outs[0], outs[1]) and bool(torch.isfinite(outs[0]).all())
+    gs.check()
 
 
 @pytest.mark.parametrize("B,heads,c,N", [(2, 1, 96, 16384), (2, 2, 48, 4096), (2, 4, 48, 1024), (1, 8, 48, 256), (2, 4, 96, 256), (8, 8, 48, 256)])
