@@ -124,7 +124,7 @@ __global__ __launch_bounds__(256) void conv_few_out_kernel(const float* __restri
 }
 
 // dW[co][ci][3][3] += sum_{b,y,x} dY[b][co][y][x] * X[b][ci][y+i-1][x+j-1]   for NCO <= 4 output channels (3x3, pad 1).
-// Rolling-row strips (as the depthwise backward, pointwise.hip): a thread owns 4 pixels x RS rows of one (b, ci) plane
+// Rolling-row strips (as the depthwise backward, stencil.hip): a thread owns 4 pixels x RS rows of one (b, ci) plane
 // of X, keeps three rows in registers and 9*NCO sums; G = lanes that share a plane (256 / 64 / gsub).
 struct Row6 { float v[6]; };
 __device__ __forceinline__ void load_row6(const float* __restrict__ plane, int H, int W, int y, int x0, Row6& r) {

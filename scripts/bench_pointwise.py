@@ -37,3 +37,15 @@ for (hid, H) in ((255, 128), (255, 64), (510, 32), (1021, 16)):
     t3 = tm(lambda: be.dwconv3x3(dd, w, dp, flip=True))
     t4 = tm(lambda: be.gdfn_bwd(p_, w, dg, dp, dw))
     print(f"gate_bwd hid={hid:4d} {H:3d}x{H:<3d}: plain {t0:6.1f} + wgrad {t1:6.1f} = {t0+t1:6.1f} ; gate+wgrad fused {t2:6.1f} ; + flip dwconv {t3:6.1f} = {t2+t3:6.1f} ; one pass {t4:6.1f} us")
+    g_ = torch.empty(B, hid, H, H, device="cuda")
+    t5 = tm(lambda: be.gdfn_gate_fwd(p_, w, g_))
+    print(f"gdfn_gate_fwd hid={hid:4d} {H:3d}x{H:<3d}: {t5:6.1f} us")
+
+# the qkv depthwise convolution (3 * dim channels) of the four levels
+for (C, H) in ((144, 128), (288, 64), (576, 32), (1152, 16)):
+    x, dy = torch.randn(B, C, H, H, device="cuda"), torch.randn(B, C, H, H, device="cuda")
+    w = torch.randn(C, 9, device="cuda") * 0.3
+    y, dw = torch.empty_like(x), torch.zeros(C, 9, device="cuda")
+    print(f"dwconv3x3       C={C:4d} {H:3d}x{H:<3d}: {tm(lambda: be.dwconv3x3(x, w, y)):6.1f} us")
+    print(f"dwconv3x3(flip) C={C:4d} {H:3d}x{H:<3d}: {tm(lambda: be.dwconv3x3(dy, w, y, flip=True)):6.1f} us")
+    print(f"dwconv3x3_bwd   C={C:4d} {H:3d}x{H:<3d}: {tm(lambda: be.dwconv3x3_bwd(dy, x, w, y, dw)):6.1f} us")

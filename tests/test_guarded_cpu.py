@@ -134,7 +134,7 @@ def test_row_sumsq_refuses_a_misaligned_operand(addr):
 
 
 def test_float4_stencils_and_ln_bwd_refuse_misaligned_operands(addr):
-    """the same omission in the other entry points of csrc/pointwise.hip that cast a caller's pointer to float4: each vector-accessed
+    """the same omission in the other entry points of csrc/pointwise.hip and csrc/stencil.hip that cast a caller's pointer to float4: each vector-accessed
     operand, 4 bytes off, is refused; planes with a side that is no multiple of 4 take scalar kernels and are not asked for it"""
     from rcot_amd import lib
     L = lib.load()

@@ -475,6 +475,66 @@ def test_gdfn_bwd_one_pass(hip, B, hid, H, W):
                    T(4, 2 * hid, 9)], [3, 4])
 
 
+# ---- strips of 8 and 16 rows.  Every shape above has too few strip threads to leave RS = 4; these are the smallest that cross the
+# dispatch thresholds of csrc/stencil.hip (200 000 threads for rcot_gdfn_bwd, 400 000 for the other two), restated here:
+def _strip_ladder(planes, H, W, threshold):
+    """(G, RS, gsub) that strip_plan of csrc/stencil.hip chooses: RS rows per strip, G lanes sharing a plane (0: not fused)"""
+    cols = planes * (W // 4)
+    rs = next((r for r in (16, 8) if cols * -(-H // r) >= threshold), 4)
+    tpp = -(-H // rs) * (W // 4)
+    if tpp % 256 == 0:
+        return 256, rs, 64
+    if tpp % 64 == 0:
+        return 64, rs, 64
+    if tpp < 64 and tpp & (tpp - 1) == 0:
+        return 1, rs, tpp
+    return 0, rs, 0
+
+
+def _last_kernel(be):
+    import ctypes
+    buf = ctypes.create_string_buffer(192)
+    be.L.rcot_last_kernel(buf, 192)
+    return buf.value.decode()
+
+
+# (1, 3125, 24, 128): ragged, the second strip has 8 live rows (the `y < H` and `r < H` arms, the halo row below a short strip);
+# (2, 12500, 12, 16): ragged, sub-wave groups of 8 lanes
+@pytest.mark.parametrize("B,hid,H,W,G,RS,gsub", [(2, 391, 128, 128, 256, 16, 64), (1, 3125, 24, 128, 64, 16, 64),
+                                                 (1, 1563, 64, 64, 64, 8, 64), (2, 12500, 12, 16, 1, 8, 8)])
+def test_gdfn_bwd_one_pass_tall_strips(hip, B, hid, H, W, G, RS, gsub):
+    assert _strip_ladder(B * hid, H, W, 200000) == (G, RS, gsub)
+
+    def fn(be, p, w, dg, dp, dw):
+        be.gdfn_bwd(p, w, dg, dp, dw)
+        if be is hip:
+            assert _last_kernel(hip) == f"gdfn_bwd_kernel<{G}, {RS}>"
+    both(hip, fn, [T(1, B, 2 * hid, H, W), T(2, 2 * hid, 9, scale=0.5), T(3, B, hid, H, W), torch.zeros(B, 2 * hid, H, W),
+                   T(4, 2 * hid, 9)], [3, 4])
+
+
+# (1, 2084, 504, 24): W/4 = 6 does not divide 64, the scalar-halo form; 32 strips, the last 8 rows tall
+@pytest.mark.parametrize("B,C,H,W,G,RS", [(2, 782, 128, 128, 256, 16), (1, 2084, 504, 24, 64, 16), (1, 1563, 128, 64, 256, 8),
+                                          (1, 3126, 64, 64, 64, 8)])
+def test_dwconv_bwd_one_pass_tall_strips(hip, B, C, H, W, G, RS):
+    assert _strip_ladder(B * C, H, W, 400000) == (G, RS, 64)
+
+    def fn(be, dy, x, w, dx, dw):
+        be.dwconv3x3_bwd(dy, x, w, dx, dw)
+    both(hip, fn, [T(1, B, C, H, W), T(2, B, C, H, W), T(3, C, 9), torch.zeros(B, C, H, W), T(4, C, 9)], [3, 4])
+
+
+# (1, 6250, 24, 128): ragged, the second strip has 8 live rows
+@pytest.mark.parametrize("B,hid,H,W,G,RS", [(2, 782, 128, 128, 256, 16), (1, 1563, 128, 64, 256, 8), (1, 6250, 24, 128, 64, 16)])
+def test_gdfn_gate_bwd_fused_wgrad_tall_strips(hip, B, hid, H, W, G, RS):
+    assert _strip_ladder(B * hid, H, W, 400000) == (G, RS, 64)
+
+    def fn(be, p, w, dg, dd, dw):
+        be.gdfn_gate_bwd(p, w, dg, dd, dw=dw)
+    both(hip, fn, [T(1, B, 2 * hid, H, W), T(2, 2 * hid, 9, scale=0.5), T(3, B, hid, H, W), torch.zeros(B, 2 * hid, H, W),
+                   T(4, 2 * hid, 9)], [3, 4])
+
+
 # ----------------------------------------------------------------------------- dense convolutions
 CONVS = [(2, 3, 48, 16, 16, 3, 1, 1), (2, 48, 24, 16, 16, 3, 1, 1), (1, 192, 384, 8, 8, 3, 1, 1), (2, 96, 3, 16, 24, 3, 1, 1),
          (2, 3, 64, 32, 32, 5, 1, 2), (2, 64, 64, 32, 32, 4, 2, 1), (2, 64, 128, 16, 16, 3, 1, 1), (2, 512, 512, 4, 4, 4, 2, 1),
