@@ -25,7 +25,7 @@ extern "C" {
 
 /* Bumped on EVERY signature change; returned by rcot_abi_version() (csrc/api.hip) and compared by the loader
  * (rcot_amd/lib.py ABI_VERSION, tests/test_abi.py) so that a stale prebuilt .so is refused, not mis-called. */
-#define RCOT_ABI_VERSION 29
+#define RCOT_ABI_VERSION 30
 
 /* Arithmetic of the MFMA products of the three GEMM-shaped entry points that take `prec` (rcot_gemm_kmajor,
  * rcot_conv1x1_wgrad, rcot_bmm_nt); operands and results are fp32 in memory either way.
@@ -518,6 +518,20 @@ int rcot_view_gather(const float* img, int planes, int H, int W, const int* ys, 
                      int Th, int Tw, float* views, void* stream);
 int rcot_view_blend(const float* views, int planes, int H, int W, const int* ys, int ny, const int* xs, int nx, const int* modes, int nm,
                     int Th, int Tw, const float* wy, const float* wx, float* out, void* stream);
+
+/* ---- MATLAB-rule bicubic resize, one axis per launch (csrc/resize.hip, where the rule is defined; rcot_amd/resize.py) ---------------------
+ * The degradation of the super-resolution task: an antialiased separable cubic resample of whole images, two launches per resize.
+ *   src : dense [planes][H][W].   dst : [planes][out_len][W] for axis 0 (rows), [planes][H][out_len] for axis 1 (columns).
+ *   idx int [out_len][K], taps float [out_len][K] : DEVICE arrays, the rule evaluated on the host for (input length, out_len); the
+ *   indices are already mirrored into [0, input length).  For every output, in fp32:
+ *       acc = 0;   for k ascending: acc = acc + taps[o][k] * src[idx[o][k]]        (each product and each sum rounded, no contraction)
+ *   so a numpy fp32 restatement matches bit for bit.  The kernel clamps every index it reads into [0, input length - 1]: a malformed
+ *   table cannot read outside the image.  Any H, W, out_len >= 1 and any alignment (float4 rows where W and the pointers allow).
+ *   No atomics, no workspace.
+ *  RCOT_EINVAL (nothing is launched, dst is untouched): a null pointer; planes, H, W, out_len or K < 1; axis outside {0, 1}.
+ *  RCOT_EUNSUPPORTED (the same): K > 64 (x4 shrink needs 18, x8 needs 34); a source or destination plane of 2^31 elements or more. */
+int rcot_resize_axis(const float* src, float* dst, long planes, int H, int W, int axis, int out_len, const int* idx, const float* taps,
+                     int K, void* stream);
 
 #ifdef __cplusplus
 }

@@ -3,7 +3,8 @@
 [0, 1].  The host keeps what needs a file system and an image decoder — the sample lists (:63-169, same list files,
 same replication factors, same clean/ground-truth naming rules :198-213) and PIL decoding — and hands every decoded uint8
 image to ONE device kernel (``rcot_patch_prep``) that crops, applies the dihedral augmentation, adds the Gaussian noise of
-the denoise_* tasks and converts to CHW float (rcot_amd/csrc/dataprep.hip).  The reference does those steps with
+the denoise_* tasks and converts to CHW float (rcot_amd/csrc/dataprep.hip).  The sr_x2 / sr_x3 / sr_x4 tasks (``--sr_dir``) degrade
+the whole HR image on the device first (rcot_amd/resize.py) and hand both images to the same kernel.  The reference does those steps with
 PIL/numpy on the host at ``num_workers=0`` (trainer.py:32,134).
 
 Randomness: the reference leaves python's ``random`` and numpy unseeded; here every draw (epoch
@@ -22,6 +23,10 @@ import torch
 DE_DICT = {"denoise_15": 0, "denoise_25": 1, "denoise_50": 2, "derain": 3, "dehaze": 4, "deblur": 5, "lowlight": 6,
            "single": 7}                                   # util/dataset_utils.py:40
 NOISE_SIGMA = {0: 15.0, 1: 25.0, 2: 50.0}                  # util/degradation_utils.py:29-40
+# superset: super-resolution (the reference's README lists DIV2K next to the other tasks and has no loader for it).  The sample is an
+# HR image, the degradation is made on the device (rcot_amd/resize.py: bicubic down by s, 8 bits, up by s, 8 bits), the label is the
+# reference's `single` — how the reference would see a pre-made SR folder
+SR_SCALE = {"sr_x2": 2, "sr_x3": 3, "sr_x4": 4}
 
 
 def crop_to_multiple(img: np.ndarray, base: int = 16) -> np.ndarray:
@@ -73,7 +78,19 @@ def build_sample_ids(args) -> List[dict]:
                                  f"util/dataset_utils.py:134-169 reads args.{attr})")
             names = sorted(os.listdir(os.path.join(root, sub_c if t == "deblur" else sub_d)))
             ids += [{"file": os.path.join(root, sub_d, n), "de": lab, "gt": os.path.join(root, sub_c, n)} for n in names] * rep
+    for t, scale in SR_SCALE.items():
+        if t in de_type:
+            root = sr_dir_or_exit(args, t)
+            names = sorted(n for n in os.listdir(root) if os.path.isfile(os.path.join(root, n)))
+            ids += [{"file": os.path.join(root, n), "de": DE_DICT["single"], "gt": None, "sr": scale} for n in names] * 5   # x5: `single`'s factor
     return ids
+
+
+def sr_dir_or_exit(args, de_type: str) -> str:
+    root = getattr(args, "sr_dir", None)
+    if root is None:
+        raise SystemExit(f"--de_type {de_type} needs --sr_dir DIR, a flat folder of high-resolution images")
+    return root
 
 
 def _read_rgb(path: str) -> np.ndarray:
@@ -119,6 +136,8 @@ class FolderLoader:
     def _decode(sid: dict):
         """worker thread: read + decode + crop to a multiple of 16 (util/image_utils.py:59-64)"""
         img = crop_to_multiple(_read_rgb(sid["file"]), 16)
+        if sid.get("sr"):                                                   # then to a multiple of the scale, at the top left (x3 only)
+            img = img[:img.shape[0] - img.shape[0] % sid["sr"], :img.shape[1] - img.shape[1] % sid["sr"]]
         gt = crop_to_multiple(_read_rgb(sid["gt"]), 16) if sid["gt"] is not None else None
         return np.ascontiguousarray(img), (None if gt is None else np.ascontiguousarray(gt))
 
@@ -133,7 +152,11 @@ class FolderLoader:
         nseed = rng.getrandbits(63)
         dev = self.be.device
         a = torch.from_numpy(img).to(dev, non_blocking=True)
-        if gt is None:        # denoise_*: the file IS the clean image, the degradation is synthetic noise
+        if sid.get("sr"):     # super-resolution: the file is the HR image; the WHOLE image is degraded, so the crop sees real neighbours
+            from .resize import sr_degrade_u8
+            assert getattr(self.be, "_plan", None) is None                  # loader launches stay outside recorded launch plans
+            self.be.patch_prep(a, sr_degrade_u8(a, sid["sr"], self.be), y0, x0, P, mode, 0.0, nseed, deg_out, clean_out)
+        elif gt is None:      # denoise_*: the file IS the clean image, the degradation is synthetic noise
             self.be.patch_prep(a, None, y0, x0, P, mode, NOISE_SIGMA[sid["de"]], nseed, deg_out, clean_out)
         else:
             g = torch.from_numpy(gt).to(dev, non_blocking=True)

@@ -9,7 +9,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 29     # == RCOT_ABI_VERSION in include/rcot_hip.h (checked by tests/test_abi.py and at load time)
+ABI_VERSION = 30     # == RCOT_ABI_VERSION in include/rcot_hip.h (checked by tests/test_abi.py and at load time)
 PREC_FP32, PREC_BF16X3, PREC_BF16X6, PREC_BF16X1 = 0, 1, 2, 3     # RCOT_PREC_* of include/rcot_hip.h
 LIB_PATH = os.environ.get("RCOT_LIB") or os.path.join(_HERE, "librcot_hip.so")   # RCOT_LIB: A/B builds while tuning
 
@@ -125,6 +125,8 @@ SIGNATURES = {
     # views of an image and their weighted blend: tiles and the x8 self-ensemble (csrc/views.hip)
     "rcot_view_gather": [_f, _i, _i, _i, _f, _i, _f, _i, _f, _i, _i, _i, _f, _f],             # ys, xs, modes: HOST int arrays
     "rcot_view_blend": [_f, _i, _i, _i, _f, _i, _f, _i, _f, _i, _i, _i, _f, _f, _f, _f],       # ys, xs, modes: HOST int arrays
+    # MATLAB-rule bicubic resize, one axis per launch (csrc/resize.hip)
+    "rcot_resize_axis": [_f, _f, _l, _i, _i, _i, _i, _f, _f, _i, _f],                          # idx, taps: DEVICE arrays
 }
 
 _lib = None

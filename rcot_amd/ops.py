@@ -1423,6 +1423,29 @@ class HipBackend:
         _lib.check(self.L.rcot_view_blend(views.data_ptr(), *a, _ptr(wy), _ptr(wx), out.data_ptr(), self._st()), "rcot_view_blend")
         return out
 
+    # ------------------------------------------------------------------ MATLAB-rule bicubic resize, one axis per launch (csrc/resize.hip)
+    def resize_axis(self, src, axis: int, idx, taps, out=None):
+        """src float [..., H, W] (dense) -> [..., out_len, W] (axis 0) or [..., H, out_len] (axis 1): out = sum_k taps[o, k] *
+        src[idx[o, k]] along the axis, in fp32, k ascending (rcot_resize_axis).  idx int32 / taps float32 [out_len, K] on the device,
+        as ``rcot_amd.resize.cubic_taps`` makes them."""
+        self._dense_planes(src, "resize_axis")
+        self._chk(taps, "resize_axis")
+        if idx.dtype != torch.int32 or not idx.is_cuda or idx.dim() != 2 or tuple(idx.shape) != tuple(taps.shape) or \
+                not idx.is_contiguous() or not taps.is_contiguous():
+            raise _lib.RcotKernelError("resize_axis: idx (int32) and taps (float32) must be dense [out_len, K] tables on the HIP device")
+        H, W = src.shape[-2:]
+        planes = src.numel() // (H * W) if H * W else 0
+        out_len, K = idx.shape
+        shape = (*src.shape[:-2], out_len, W) if axis == 0 else (*src.shape[:-2], H, out_len)
+        if out is None:
+            out = self.empty(*shape)
+        self._dense_planes(out, "resize_axis")
+        if tuple(out.shape) != shape:
+            raise _lib.RcotKernelError(f"resize_axis: out must be {shape}")
+        _lib.check(self.L.rcot_resize_axis(src.data_ptr(), out.data_ptr(), planes, H, W, int(axis), out_len, idx.data_ptr(),
+                                           taps.data_ptr(), K, self._st()), "rcot_resize_axis")
+        return out
+
     # ------------------------------------------------------------------ standard image-quality figures (csrc/quality.hip)
     WINDOWS = {"uniform7": 0, "gauss11": 1}
     SPACES = {"rgb": 0, "y": 1}

@@ -38,6 +38,15 @@ util/val_utils.py:50-66), gauss11 = the 11 x 11, sigma 1.5 Gaussian window (basi
 BT.601 luma (deraining tables).  ``--metrics folders`` computes them on the host from the PNGs read back, ``--metrics device`` with
 rcot_image_quality on the 8-bit images already on the device.  A line naming the protocol is printed before the report.  The defaults
 (box2, rgb) print what the reference prints.
+
+Superset: ``--sr_scale S`` evaluates super-resolution (the reference's README: "the LR images undergo bicubic rescaling to match the
+dimensions of their respective high-resolution counterparts"): the network's input is the bicubic degradation made on the device
+(rcot_amd/resize.py; MATLAB's imresize rule, csrc/resize.hip).  ``--sr_from target`` (default) makes it from the target — cropped at the
+top left to a multiple of S, shrunk, quantised to 8 bits, enlarged, quantised; ``--degset`` is not read.  ``--sr_from lr`` reads the
+h x w LR images from ``--degset``, enlarges them by S and crops the target at the top left to hS x wS (targets smaller than that, or
+larger by S or more in either direction, are skipped with a message).  ``--savedeg DIR`` writes the 8-bit network input — the bicubic
+baseline every SR table starts with.  The padding, tiling, ensemble and metrics flags combine with these as before (``--color y
+--ssim_window gauss11`` is the protocol of SR tables); ``--sr_scale 0`` leaves everything as it was.
 """
 from __future__ import annotations
 
@@ -79,6 +88,14 @@ parser.add_argument("--ssim_window", choices=["box2", "uniform7", "gauss11"], de
                          "tables); gauss11 = the 11 x 11, sigma 1.5 Gaussian window (basicsr / MATLAB-style)")
 parser.add_argument("--color", choices=["rgb", "y"], default="rgb",
                     help="superset: y = PSNR / SSIM on the BT.601 luma of YCbCr (deraining tables) instead of the three RGB planes")
+parser.add_argument("--sr_scale", type=int, default=0,
+                    help="superset: super-resolution by this integer factor: the network's input is the bicubic degradation made on the "
+                         "device (rcot_amd/resize.py); 0 = off, everything as before")
+parser.add_argument("--sr_from", choices=["target", "lr"], default="target",
+                    help="superset, with --sr_scale S: target = degrade the target (cropped at the top left to a multiple of S; --degset is "
+                         "not read); lr = --degset holds the h x w low-resolution images, enlarged by S, the target is cropped to hS x wS")
+parser.add_argument("--savedeg", default=None, type=str, help="superset: also write the 8-bit network input (with --sr_scale: the bicubic "
+                                                             "baseline) as PNGs under this folder")
 
 
 # ------------------------------------------------------------------------------- metrics (evaluate.py)
@@ -193,6 +210,27 @@ def _report(psnr, ssim, pmax, smax, pmin, smin, done, ssim_window="box2", color=
                 ssim_window=ssim_window, color=color)
 
 
+def _sr_pair(deg: np.ndarray, tar: np.ndarray, S: int, from_target: bool, be):
+    """``--sr_scale S``: (network input, target) as uint8 [H, W, 3] arrays of one size, or None (with a message) for a pair that is
+    skipped.  from_target: the target is cropped at the top left to a multiple of S and degraded (down, 8 bits, up, 8 bits).  Else
+    ``deg`` is the h x w LR image: it is enlarged to hS x wS, and the target is cropped to that at the top left — it may be larger by
+    less than S in either direction (what the crop to a multiple of S removed when the LR image was made)."""
+    from .resize import sr_degrade_u8, sr_upscale_u8
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(be.device)
+    if from_target:
+        H, W = tar.shape[0] - tar.shape[0] % S, tar.shape[1] - tar.shape[1] % S
+        if H < S or W < S:
+            print(f"  skipped: target {tar.shape[0]} x {tar.shape[1]} is smaller than the scale factor {S}")
+            return None
+        tar = np.ascontiguousarray(tar[:H, :W])
+        return sr_degrade_u8(up(tar), S, be).cpu().numpy(), tar
+    H, W = deg.shape[0] * S, deg.shape[1] * S
+    if tar.shape[0] < H or tar.shape[1] < W or tar.shape[0] - H >= S or tar.shape[1] - W >= S:
+        print(f"  skipped: LR {deg.shape[0]} x {deg.shape[1]} times {S} is {H} x {W}, the target is {tar.shape[0]} x {tar.shape[1]}")
+        return None
+    return sr_upscale_u8(up(deg), H, W, be).cpu().numpy(), np.ascontiguousarray(tar[:H, :W])
+
+
 def _main_any_size(opt, net):
     """``--pad`` other than none and / or ``--metrics device``: ingest (or pad2d for the noisy float input), the network on the padded
     image, and the egress kernel for the crop, the three 8-bit images and the statistics.  The size multiple is the network's own."""
@@ -203,7 +241,10 @@ def _main_any_size(opt, net):
     device_metrics = opt.metrics == "device"
     standard = _standard(opt)                                         # rcot_image_quality instead of the egress kernel's own sums
     proto = (opt.ssim_window, opt.color)
-    deg_list, tar_list = sorted(glob.glob(opt.degset + "*")), sorted(glob.glob(opt.tarset + "*"))
+    tar_list = sorted(glob.glob(opt.tarset + "*"))
+    S = opt.sr_scale
+    sr_target = S > 0 and opt.sr_from == "target"
+    deg_list = tar_list if sr_target else sorted(glob.glob(opt.degset + "*"))       # (sr_from target: --degset is not read)
     rng = np.random.default_rng(opt.seed)
     noisy = opt.noise_sigma is not None
     sizes, stats = [], []
@@ -211,6 +252,11 @@ def _main_any_size(opt, net):
         name = os.path.basename(tar_name)
         print("Processing ", deg_name)
         deg, tar = np.array(Image.open(deg_name).convert("RGB")), np.array(Image.open(tar_name).convert("RGB"))
+        if S > 0:
+            pair = _sr_pair(deg, tar, S, sr_target, be)
+            if pair is None:
+                continue
+            deg, tar = pair
         if deg.shape != tar.shape:
             print(f"  skipped: degraded {deg.shape[0]} x {deg.shape[1]} and target {tar.shape[0]} x {tar.shape[1]} differ")
             continue
@@ -228,6 +274,8 @@ def _main_any_size(opt, net):
             print(f"  skipped: {e}")
             continue
         tar_d = torch.from_numpy(np.ascontiguousarray(tar)).to(be.device)
+        if opt.savedeg:
+            Image.fromarray(np.ascontiguousarray(deg)).save(os.path.join(opt.savedeg, name))
         if noisy:                                                     # the noise is drawn on the host (numpy's generator, as the reference)
             x = torch.from_numpy(np.ascontiguousarray(deg.transpose(2, 0, 1))).float().div(255).unsqueeze(0)
             x = x + torch.from_numpy(rng.normal(size=tar.transpose(2, 0, 1).shape) * opt.noise_sigma / 255.0).float()
@@ -268,10 +316,12 @@ def main(argv=None):
                          "use --metrics folders, or --ssim_window uniform7 | gauss11")
     if not torch.cuda.is_available():
         raise SystemExit("No GPU found: rcot_amd.tester runs the HIP path only")
-    for d in (opt.save, opt.savetar, opt.saveres):
+    if opt.sr_scale < 0 or opt.sr_scale == 1:
+        raise SystemExit(f"--sr_scale {opt.sr_scale}: the scale factor must be an integer >= 2 (0 = off)")
+    for d in (opt.save, opt.savetar, opt.saveres) + ((opt.savedeg,) if opt.savedeg else ()):
         os.makedirs(d, exist_ok=True)
     net, mult = load_network(opt.model)
-    if opt.pad != "none" or opt.metrics == "device":
+    if opt.pad != "none" or opt.metrics == "device" or opt.sr_scale > 0:
         return _main_any_size(opt, net)
     deg_list, tar_list = sorted(glob.glob(opt.degset + "*")), sorted(glob.glob(opt.tarset + "*"))
     rng = np.random.default_rng(opt.seed)
@@ -298,6 +348,8 @@ def main(argv=None):
         if noisy:
             x = x + torch.from_numpy(rng.normal(size=tar.transpose(2, 0, 1).shape) * opt.noise_sigma / 255.0).float()
         gt = torch.from_numpy(np.ascontiguousarray(tar.transpose(2, 0, 1))).float().div(255).unsqueeze(0)
+        if opt.savedeg:
+            Image.fromarray(np.ascontiguousarray(deg)).save(os.path.join(opt.savedeg, name))
         xd = x.cuda()
         out = restore(net, xd, opt.tile, opt.overlap, mult, None, opt.tile_window, opt.tile_batch, opt.ensemble)
         res = (xd - out).cpu()

@@ -49,6 +49,9 @@ parser.add_argument("--data_file_dir", type=str, default="data_dir/")
 parser.add_argument("--deblur_dir", type=str, default=None, help="(the reference reads args.deblur_dir but defines no flag)")
 parser.add_argument("--lowlight_dir", type=str, default=None, help="(same for lowlight)")
 parser.add_argument("--single_dir", type=str, default=None, help="(same for --de_type single)")
+parser.add_argument("--sr_dir", type=str, default=None,
+                    help="--de_type sr_x2 | sr_x3 | sr_x4: a flat folder of high-resolution images; the bicubic degradation (down by the "
+                         "scale, 8 bits, up, 8 bits) is made on the device (rcot_amd/resize.py)")
 parser.add_argument("--seed", type=int, default=None, help="seed (the reference draws an unseeded random one)")
 parser.add_argument("--prec", choices=["fp32", "bf16x6", "bf16x3", "bf16x1"], default=os.environ.get("RCOT_GEMM_PREC", "fp32"),
                     help="arithmetic of the 1x1 MFMA products (include/rcot_hip.h RCOT_PREC_*; one default for HipBackend(), this CLI and "
@@ -69,6 +72,18 @@ opt: Optional[argparse.Namespace] = None
 
 DE_IDS = {"denoise_15": 0, "denoise_25": 1, "denoise_50": 2, "derain": 3, "dehaze": 4, "deblur": 5,
           "lowlight": 6, "single": 7}   # util/dataset_utils.py:40
+
+
+def check_sr_flags(o) -> None:
+    """the super-resolution tasks read HR images from --sr_dir and degrade them on the device: refused up front without the folder
+    or with --synthetic (seeded patches have no image to resize)"""
+    from .data import SR_SCALE, sr_dir_or_exit
+    sr = [t for t in o.de_type if t in SR_SCALE]
+    if not sr:
+        return
+    if o.synthetic:
+        raise SystemExit(f"--de_type {sr[0]} degrades whole images from --sr_dir: it cannot be combined with --synthetic")
+    sr_dir_or_exit(o, sr[0])
 
 
 def check_patch_size(P: int) -> int:
@@ -621,6 +636,7 @@ def main(argv=None):
         check_patch_size(opt.patch_size)                   # before any network is built or the GPU is touched
     except ValueError as e:
         raise SystemExit(str(e))
+    check_sr_flags(opt)
     # --backbone mprnet: with a GPU the older transport map runs on the HIP kernels (rcot_amd/mprnet_hip.py) through everything below —
     # data folders, data parallelism, validation, launch plans; without one (or with RCOT_MPRNET_STOCK=1) the stock-ops loop
     hip_mprnet = opt.backbone == "mprnet" and torch.cuda.is_available() and os.environ.get("RCOT_MPRNET_STOCK", "0") != "1"
