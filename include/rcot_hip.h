@@ -25,7 +25,7 @@ extern "C" {
 
 /* Bumped on EVERY signature change; returned by rcot_abi_version() (csrc/api.hip) and compared by the loader
  * (rcot_amd/lib.py ABI_VERSION, tests/test_abi.py) so that a stale prebuilt .so is refused, not mis-called. */
-#define RCOT_ABI_VERSION 30
+#define RCOT_ABI_VERSION 31
 
 /* Arithmetic of the MFMA products of the three GEMM-shaped entry points that take `prec` (rcot_gemm_kmajor,
  * rcot_conv1x1_wgrad, rcot_bmm_nt); operands and results are fp32 in memory either way.
@@ -391,6 +391,14 @@ int rcot_ot_grad(const float* degraded, const float* restored, const float* targ
  * (derain / dehaze / deblur / lowlight / single) gets the same crop and map. */
 int rcot_patch_prep(const unsigned char* deg_img, const unsigned char* clean_img, int H, int W, int y0, int x0, int P,
                     int mode, float noise_sigma, unsigned long long seed, float* deg_out, float* clean_out, void* stream);
+/* The same for a whole batch in ONE launch, from images that stay resident on the device (rcot_amd/imagecache.py): `table` is a
+ * DEVICE array of B rows of 8 int64 { clean_img, deg_img (0 = synthetic noise), W, y0, x0, mode, noise_sigma (its float32 bit
+ * pattern in the low 32 bits), seed }; deg_out / clean_out are [B][3][P][P].  Row b gives the bits rcot_patch_prep gives for the
+ * same arguments, noise included.  The rows may point at images of different sizes and may mix paired and noise samples.  The
+ * table is trusted as rcot_pack_weights' is: the CALLER checks 0 <= y0, y0 + P <= H, 0 <= x0, x0 + P <= W and 0 <= mode <= 7 for
+ * every row before it launches (HipBackend.patch_prep_batch does).  RCOT_EINVAL without a launch for B <= 0, B > 65535, P <= 0 or
+ * a null pointer. */
+int rcot_patch_prep_batch(const long long* table, int B, int P, float* deg_out, float* clean_out, void* stream);
 
 /* ---- fused flat-buffer optimizers (trainer.py:121-126) ---------------------------------------------------- */
 int rcot_rmsprop_step(float* p, const float* g, float* sq, long n, double lr, double alpha, double eps,

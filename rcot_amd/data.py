@@ -7,6 +7,10 @@ the denoise_* tasks and converts to CHW float (rcot_amd/csrc/dataprep.hip).  The
 the whole HR image on the device first (rcot_amd/resize.py) and hand both images to the same kernel.  The reference does those steps with
 PIL/numpy on the host at ``num_workers=0`` (trainer.py:32,134).
 
+``FolderLoader(..., cache=DeviceImageCache(...))`` (the trainer's ``--data_cache device``, rcot_amd/imagecache.py) keeps every decoded
+image — and the degraded twin of an HR image — on the device after its first use and cuts a whole batch from the resident images in ONE
+launch (``rcot_patch_prep_batch``); the batches are the uncached loader's, bit for bit.
+
 Randomness: the reference leaves python's ``random`` and numpy unseeded; here every draw (epoch
 shuffle, crop origin, augmentation mode 1..7, noise seed) comes from one ``random.Random(seed, epoch)`` stream indexed by
 the GLOBAL sample position, so a run is reproducible and the union of the ranks' shards does not depend on the world size.
@@ -102,10 +106,15 @@ class FolderLoader:
     """Iterable over one epoch of shuffled batches (``len`` = batches per epoch of the GLOBAL batch size), sharded over
     ranks by global sample position.  Yields device tensors."""
 
-    def __init__(self, args, local_batch: int, seed: int = 0, rank: int = 0, world: int = 1, backend=None, threads: int = 0):
+    def __init__(self, args, local_batch: int, seed: int = 0, rank: int = 0, world: int = 1, backend=None, threads: int = 0, cache=None):
         """``threads`` (the reference's --threads / DataLoader num_workers, trainer.py:32,134): decode workers.  The files of
         the NEXT batches are read and decoded in a thread pool while the current iteration runs (PIL releases the GIL while it
         decodes); 0 still prefetches with one worker — decoding never sits on the training thread's critical path."""
+        # ``cache`` (a rcot_amd.imagecache.DeviceImageCache on the backend's device, or None): None is the route above, launch for
+        # launch.  With a cache every file is decoded and uploaded once and stays on the device, the pool decodes only the files of
+        # coming batches that are not resident yet, and a batch is ONE rcot_patch_prep_batch launch — the same draws from the same
+        # per-sample streams, so the batches are the uncached loader's bit for bit (``_iter_cached``).
+        self.cache = cache
         self.args, self.B, self.P = args, local_batch, args.patch_size
         self.threads = max(1, int(threads or 0))
         self.depth = 2                                                      # batches decoded ahead
@@ -163,6 +172,11 @@ class FolderLoader:
             self.be.patch_prep(g, a, y0, x0, P, mode, 0.0, nseed, deg_out, clean_out)
 
     def __iter__(self):
+        if self.cache is not None:
+            return self._iter_cached()
+        return self._iter_uncached()
+
+    def _iter_uncached(self):
         from concurrent.futures import ThreadPoolExecutor
         self.epoch += 1
         order = list(range(len(self.ids)))
@@ -197,4 +211,100 @@ class FolderLoader:
                     self._sample(rng, sid, deg[j], clean[j], futs[j].result())
                     names.append(os.path.basename(sid["gt"] or sid["file"]).split(".")[0])
                     labels.append(sid["de"])
+                yield ([names, torch.tensor(labels)], deg, clean)
+
+    # ------------------------------------------------------------------ the cached route (rcot_amd/imagecache.py)
+    @staticmethod
+    def _file_keys(sid: dict):
+        """the files of a sample as (cache key, path, sr scale or 0): the image, then the ground truth of a paired sample"""
+        if sid.get("sr"):
+            return [((sid["file"], "crop16", "mod", sid["sr"]), sid["file"], sid["sr"])]
+        keys = [((sid["file"], "crop16"), sid["file"], 0)]
+        if sid["gt"] is not None:
+            keys.append(((sid["gt"], "crop16"), sid["gt"], 0))
+        return keys
+
+    @staticmethod
+    def _decode_file(path: str, s: int) -> np.ndarray:
+        """worker thread: what ``_decode`` does to one file"""
+        img = crop_to_multiple(_read_rgb(path), 16)
+        if s:
+            img = img[:img.shape[0] - img.shape[0] % s, :img.shape[1] - img.shape[1] % s]
+        return np.ascontiguousarray(img)
+
+    def _iter_cached(self):
+        from concurrent.futures import ThreadPoolExecutor
+        self.epoch += 1
+        cache = self.cache
+        order = list(range(len(self.ids)))
+        random.Random(self.seed * 1_000_003 + self.epoch).shuffle(order)
+        g = self.B * self.world
+        dev = self.be.device
+        nb = len(self)
+        P = self.P
+        batch_idx = lambda it: order[it * g + self.rank * self.B:it * g + self.rank * self.B + self.B]
+        with ThreadPoolExecutor(max_workers=self.threads) as pool:
+            inflight = {}                                                   # key -> future of a file that is being decoded
+            asked = set()
+
+            def submit(it):
+                if it < nb and it not in asked:
+                    asked.add(it)
+                    for k in batch_idx(it):
+                        for key, path, s in self._file_keys(self.ids[k]):
+                            if key not in cache and key not in inflight:
+                                inflight[key] = pool.submit(self._decode_file, path, s)
+
+            def resident(key, path, s, local):
+                """the device image of a file: from the cache, from this batch's transients, else decoded (by the pool, as a rule)"""
+                t = cache.lookup(key)
+                if t is None:
+                    t = local.get(key)
+                if t is None:
+                    fut = inflight.pop(key, None)
+                    img = fut.result() if fut is not None else self._decode_file(path, s)
+                    t = local[key] = cache.offer(key, torch.from_numpy(img).to(dev, non_blocking=True))
+                return t
+
+            for it in range(min(self.depth, nb)):
+                submit(it)
+            for it in range(nb):
+                lo = it * g + self.rank * self.B
+                idx = batch_idx(it)
+                if not idx:
+                    break
+                submit(it)
+                submit(it + self.depth)
+                n = len(idx)
+                deg = torch.empty(n, 3, P, P, dtype=torch.float32, device=dev)
+                clean = torch.empty_like(deg)
+                names, labels, rows, local = [], [], [], {}
+                for j, k in enumerate(idx):
+                    sid = self.ids[k]
+                    rng = random.Random((self.seed * 1_000_003 + self.epoch) * 2_147_483_659 + lo + j)
+                    imgs = [resident(key, path, s, local) for key, path, s in self._file_keys(sid)]
+                    a, gt = imgs[0], (imgs[1] if len(imgs) > 1 else None)
+                    H, W = a.shape[0], a.shape[1]
+                    if H < P or W < P or (gt is not None and gt.shape != a.shape):
+                        raise ValueError(f"{sid['file']}: {H}x{W} is smaller than the {P}x{P} patch or differs from its ground truth")
+                    y0, x0 = rng.randint(0, H - P), rng.randint(0, W - P)   # the draws of _sample, in its order
+                    mode = rng.randint(1, 7)
+                    nseed = rng.getrandbits(63)
+                    if sid.get("sr"):
+                        key = (sid["file"], "sr", sid["sr"])
+                        d = cache.lookup(key)
+                        if d is None:
+                            d = local.get(key)
+                        if d is None:
+                            from .resize import sr_degrade_u8
+                            d = local[key] = cache.offer(key, sr_degrade_u8(a, sid["sr"], self.be))
+                            cache.sr_degradations += 1
+                        rows.append((a, d, y0, x0, mode, 0.0, nseed))
+                    elif gt is None:
+                        rows.append((a, None, y0, x0, mode, NOISE_SIGMA[sid["de"]], nseed))
+                    else:
+                        rows.append((gt, a, y0, x0, mode, 0.0, nseed))
+                    names.append(os.path.basename(sid["gt"] or sid["file"]).split(".")[0])
+                    labels.append(sid["de"])
+                self.be.patch_prep_batch(rows, P, deg, clean)
                 yield ([names, torch.tensor(labels)], deg, clean)

@@ -1,0 +1,60 @@
+"""A device-resident training set: every image of the training folders decoded once and kept in HBM as uint8 [H, W, 3], so that
+``FolderLoader(..., cache=...)`` (rcot_amd/data.py) cuts a whole batch from resident images in one launch (``patch_prep_batch``)
+instead of decoding, uploading and — for the super-resolution tasks — degrading the files of every sample again.
+
+Keys
+    (path, "crop16")            a decoded file after ``crop_to_multiple(..., 16)``
+    (path, "crop16", "mod", s)  the HR image of an ``sr_x<s>`` sample after the further top-left crop to a multiple of ``s``
+    (path, "sr", s)             its degraded twin, made ONCE by ``rcot_amd.resize.sr_degrade_u8``
+
+Budget: ``budget_bytes`` of image bytes.  An image that would take the total over the budget is not stored: the loader uses it as a
+transient tensor for the batch at hand (stream-ordered allocation keeps it alive until the launch has run) and meets it as a miss
+again next time.  There is no eviction and no reordering: what is resident depends only on the order of first touches, which the
+loader's seed fixes, so a run stays reproducible.
+
+Counters: ``images`` and ``bytes`` resident, ``hits`` and ``misses`` over every resolution of a key, ``sr_degradations`` made.
+"""
+from __future__ import annotations
+
+import torch
+
+
+class DeviceImageCache:
+    def __init__(self, backend, budget_bytes: int):
+        self.be = backend
+        self.device = backend.device
+        self.budget = max(0, int(budget_bytes))
+        self._store = {}
+        self.bytes = self.hits = self.misses = self.sr_degradations = 0
+
+    @property
+    def images(self) -> int:
+        return len(self._store)
+
+    def __contains__(self, key) -> bool:
+        return key in self._store
+
+    def keys(self):
+        return list(self._store)                      # in the order of storing
+
+    def lookup(self, key):
+        """the resident image of ``key`` (a hit) or None (a miss); every call counts as one of the two"""
+        t = self._store.get(key)
+        if t is None:
+            self.misses += 1
+        else:
+            self.hits += 1
+        return t
+
+    def offer(self, key, img: torch.Tensor) -> torch.Tensor:
+        """``img`` (uint8 [H, W, 3] on the cache's device) is kept under ``key`` if it fits the budget; returned either way"""
+        if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3 or not img.is_contiguous() or img.device != self.device:
+            raise ValueError(f"DeviceImageCache: {key}: expected a contiguous uint8 [H, W, 3] image on {self.device}")
+        if key not in self._store and self.bytes + img.numel() <= self.budget:
+            self._store[key] = img
+            self.bytes += img.numel()
+        return img
+
+    def report(self) -> str:
+        return (f"data cache: {self.images} images, {self.bytes / 2 ** 20:.1f} MiB of {self.budget / 2 ** 30:g} GiB, {self.hits} hits, "
+                f"{self.misses} misses, {self.sr_degradations} sr degradations")

@@ -13,6 +13,7 @@ from __future__ import annotations
 from typing import Optional, Sequence, Tuple
 
 import os
+import struct
 import sys
 
 import ctypes as C
@@ -29,6 +30,35 @@ ctypes_ll = C.c_longlong
 
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
+
+
+def check_patch_rows(rows, P: int, deg_out, clean_out) -> None:
+    """The host check of ``patch_prep_batch`` (backend-independent: the kernel trusts its table): every row is
+    ``(clean_img, deg_img | None, y0, x0, mode, sigma, seed)`` with contiguous uint8 [H, W, 3] images of one shape per pair, a P x P
+    window inside the image and a mode in 0..7; ``deg_out`` / ``clean_out`` are contiguous float32 [len(rows), 3, P, P].  Raises
+    ValueError naming the first row that fails."""
+    P = int(P)
+    if P <= 0 or not rows:
+        raise ValueError(f"patch_prep_batch: needs at least one row and P > 0, got {len(rows)} row(s), P = {P}")
+    for what, t in (("deg_out", deg_out), ("clean_out", clean_out)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (len(rows), 3, P, P):
+            raise ValueError(f"patch_prep_batch: {what} must be a contiguous float32 [{len(rows)}, 3, {P}, {P}] tensor, got "
+                             f"{t.dtype} {tuple(t.shape)}")
+    for b, (clean_img, deg_img, y0, x0, mode, sigma, seed) in enumerate(rows):
+        for what, t in (("clean", clean_img), ("degraded", deg_img)):
+            if t is None and what == "degraded":
+                continue
+            if t is None or t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or not t.is_contiguous():
+                raise ValueError(f"patch_prep_batch: row {b}: the {what} image must be a contiguous uint8 [H, W, 3] tensor")
+            if t.device != deg_out.device:
+                raise ValueError(f"patch_prep_batch: row {b}: the {what} image is on {t.device}, the batch on {deg_out.device}")
+        H, W = int(clean_img.shape[0]), int(clean_img.shape[1])
+        if deg_img is not None and tuple(deg_img.shape) != (H, W, 3):
+            raise ValueError(f"patch_prep_batch: row {b}: the degraded image is {tuple(deg_img.shape)}, the clean one {(H, W, 3)}")
+        if not (0 <= int(y0) and int(y0) + P <= H and 0 <= int(x0) and int(x0) + P <= W):
+            raise ValueError(f"patch_prep_batch: row {b}: the {P} x {P} window at ({y0}, {x0}) leaves the {H} x {W} image")
+        if not 0 <= int(mode) <= 7:
+            raise ValueError(f"patch_prep_batch: row {b}: mode {mode} is not one of the dihedral maps 0..7")
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None) or (lambda i: torch.cuda.current_stream(i).cuda_stream)
@@ -1306,6 +1336,24 @@ class HipBackend:
         _lib.check(self.L.rcot_patch_prep(_ptr(deg_img), clean_img.data_ptr(), H, W, y0, x0, P, mode, float(sigma),
                                           int(seed) & 0xFFFFFFFFFFFFFFFF, deg_out.data_ptr(), clean_out.data_ptr(), self._st()),
                    "rcot_patch_prep")
+
+    def patch_prep_batch(self, rows, P: int, deg_out, clean_out):
+        """``rows``: one ``(clean_img, deg_img | None, y0, x0, mode, sigma, seed)`` per sample, the images uint8 [H, W, 3] resident on
+        the device (any sizes; None -> synthetic noise of ``sigma``); writes ``deg_out`` / ``clean_out`` [len(rows), 3, P, P] in ONE
+        launch, row b with the bits ``patch_prep`` gives (rcot_patch_prep_batch).  Every row is checked on the host first
+        (``check_patch_rows``: ValueError, nothing launched); the table travels in one pinned host tensor, one copy on the current
+        stream."""
+        assert self._plan is None                                          # loader launches stay outside recorded launch plans
+        check_patch_rows(rows, P, deg_out, clean_out)
+        flat = []
+        for clean_img, deg_img, y0, x0, mode, sigma, seed in rows:
+            s = int(seed) & 0xFFFFFFFFFFFFFFFF
+            flat += [clean_img.data_ptr(), 0 if deg_img is None else deg_img.data_ptr(), int(clean_img.shape[1]), int(y0), int(x0),
+                     int(mode), struct.unpack("<I", struct.pack("<f", float(sigma)))[0], s - (1 << 64) if s >> 63 else s]
+        # (pinned: the copy is asynchronous, and torch's host allocator keeps the block until the copy has run)
+        table = torch.tensor(flat, dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
+        _lib.check(self.L.rcot_patch_prep_batch(table.data_ptr(), len(rows), int(P), deg_out.data_ptr(), clean_out.data_ptr(),
+                                                self._st()), "rcot_patch_prep_batch")
 
     # ------------------------------------------------------------------ whole-image validation at any size (csrc/imageio.hip)
     PAD_MODES = {None: 0, "none": 0, "reflect": 1, "replicate": 2}

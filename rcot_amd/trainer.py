@@ -65,6 +65,13 @@ parser.add_argument("--backbone", choices=["restormer", "mprnet"], default="rest
 parser.add_argument("--val_pad", choices=["none", "reflect", "replicate"], default="none",
                     help="validation at any image size: pad bottom / right to the network's size multiple on the device, restore, crop "
                          "(rcot_amd/wholeimage.py); none = the reference's rule, images that are not multiples of 8 are skipped")
+parser.add_argument("--data_cache", choices=["off", "device"], default="off",
+                    help="device: every training image is decoded once and stays on the device as uint8 (a super-resolution image with "
+                         "its degraded twin, made once); a batch is cut from the resident images in one launch "
+                         "(rcot_amd/imagecache.py).  The batches are those of `off`, bit for bit.  Ignored with --synthetic")
+parser.add_argument("--data_cache_gb", type=float, default=16.0,
+                    help="--data_cache device: budget of image bytes per rank, in GiB; an image that does not fit is decoded again "
+                         "whenever a batch needs it (no eviction: what is resident depends only on the order of first touches)")
 parser.add_argument("--synthetic", action="store_true", help="seeded synthetic patches (no dataset folders needed)")
 parser.add_argument("--iters", type=int, default=20, help="iterations per epoch with --synthetic")
 
@@ -709,7 +716,11 @@ def main(argv=None):
                                  world=world, unpaired=(opt.pairnum == 0))
     else:
         from .data import FolderLoader
-        loader = FolderLoader(opt, opt.batchSize // world, seed=seed, rank=rank, world=world, threads=opt.threads)
+        cache = None
+        if opt.data_cache == "device":                                     # every rank keeps what IT touches, on its own device
+            from .imagecache import DeviceImageCache
+            cache = DeviceImageCache(default_backend(), int(opt.data_cache_gb * 2 ** 30))
+        loader = FolderLoader(opt, opt.batchSize // world, seed=seed, rank=rank, world=world, threads=opt.threads, cache=cache)
     import glob
     deg_list, tar_list = sorted(glob.glob(opt.degset + "*")), sorted(glob.glob(opt.tarset + "*"))   # :137-141
     stepper = MinimaxStep(Tnet, Fnet, T_opt, F_opt, opt.sigma, opt.Sigma)
@@ -722,6 +733,8 @@ def main(argv=None):
         if rank == 0:
             dt = time.time() - t0
             print(f"epoch {epoch}: {len(loader) * opt.batchSize / dt:.1f} patches/s")
+            if getattr(loader, "cache", None) is not None:
+                print(loader.cache.report())
             p = evaluate(Tnet, deg_list, tar_list, pad=opt.val_pad)        # :149
             os.makedirs("./checksample/" + str(opt.type), exist_ok=True)
             with open("./checksample/" + str(opt.type) + "/validation_results.txt", "a") as f:      # :151-153
