@@ -25,7 +25,7 @@ extern "C" {
 
 /* Bumped on EVERY signature change; returned by rcot_abi_version() (csrc/api.hip) and compared by the loader
  * (rcot_amd/lib.py ABI_VERSION, tests/test_abi.py) so that a stale prebuilt .so is refused, not mis-called. */
-#define RCOT_ABI_VERSION 31
+#define RCOT_ABI_VERSION 32
 
 /* Arithmetic of the MFMA products of the three GEMM-shaped entry points that take `prec` (rcot_gemm_kmajor,
  * rcot_conv1x1_wgrad, rcot_bmm_nt); operands and results are fp32 in memory either way.
@@ -540,6 +540,22 @@ int rcot_view_blend(const float* views, int planes, int H, int W, const int* ys,
  *  RCOT_EUNSUPPORTED (the same): K > 64 (x4 shrink needs 18, x8 needs 34); a source or destination plane of 2^31 elements or more. */
 int rcot_resize_axis(const float* src, float* dst, long planes, int H, int W, int axis, int out_len, const int* idx, const float* taps,
                      int K, void* stream);
+
+/* ---- baseline JPEG round trip (csrc/jpeg.hip; rcot_amd/jpeg.py, the compression-artifact task jpeg_q<Q>) ------------------------------
+ * src uint8 [H][W][3] (RGB, HWC, device) -> dst uint8 [H][W][3]: what Image.open(BytesIO(<src saved with quality, subsampling>)) holds
+ * with Pillow on libjpeg-turbo, byte for byte — colour conversion, chroma subsampling, the "islow" integer DCT, quantisation with the
+ * scaled Annex K tables and their inverses; no bitstream is made.  The rule is written out in the header comment of csrc/jpeg.hip.
+ *   quality      1 .. 100
+ *   subsampling  0: 4:4:4, one launch, no workspace (ws may be null).  2: 4:2:0 (PIL's default), two launches: the decoded Y, Cb and Cr
+ *                planes go through ws, rcot_jpeg_ws_bytes(H, W, 2) bytes of any alignment (about 1.5 bytes per pixel of the image
+ *                rounded up to tiles of 16 x 64).
+ *   32-bit integer arithmetic, no atomics, any H, W >= 1 and any alignment of src and dst; bitwise reproducible.
+ *  RCOT_EINVAL (nothing is launched, dst is untouched): src or dst null; H or W < 1; quality outside 1 .. 100; subsampling other than
+ *  0 or 2; for 4:2:0 a null or too small workspace, and W <= 4 (a codec enlarges a chroma plane of 2 samples or fewer by another rule);
+ *  an image of more than 2^20 tiles.  rcot_jpeg_ws_bytes returns the byte count (0 for 4:4:4) or RCOT_EINVAL. */
+int rcot_jpeg_ws_bytes(int H, int W, int subsampling);
+int rcot_jpeg_roundtrip(const unsigned char* src, unsigned char* dst, int H, int W, int quality, int subsampling, void* ws,
+                        size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

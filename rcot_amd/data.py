@@ -4,7 +4,8 @@
 same replication factors, same clean/ground-truth naming rules :198-213) and PIL decoding — and hands every decoded uint8
 image to ONE device kernel (``rcot_patch_prep``) that crops, applies the dihedral augmentation, adds the Gaussian noise of
 the denoise_* tasks and converts to CHW float (rcot_amd/csrc/dataprep.hip).  The sr_x2 / sr_x3 / sr_x4 tasks (``--sr_dir``) degrade
-the whole HR image on the device first (rcot_amd/resize.py) and hand both images to the same kernel.  The reference does those steps with
+the whole HR image on the device first (rcot_amd/resize.py) and hand both images to the same kernel; the jpeg_q<Q> tasks (``--jpeg_dir``)
+do the same with a baseline JPEG round trip (rcot_amd/jpeg.py).  The reference does those steps with
 PIL/numpy on the host at ``num_workers=0`` (trainer.py:32,134).
 
 ``FolderLoader(..., cache=DeviceImageCache(...))`` (the trainer's ``--data_cache device``, rcot_amd/imagecache.py) keeps every decoded
@@ -31,6 +32,39 @@ NOISE_SIGMA = {0: 15.0, 1: 25.0, 2: 50.0}                  # util/degradation_ut
 # HR image, the degradation is made on the device (rcot_amd/resize.py: bicubic down by s, 8 bits, up by s, 8 bits), the label is the
 # reference's `single` — how the reference would see a pre-made SR folder
 SR_SCALE = {"sr_x2": 2, "sr_x3": 3, "sr_x4": 4}
+# superset: compression-artifact reduction, --de_type jpeg_q<Q> for any Q in 1 .. 100 (the CAR rows of restoration tables use 10, 20,
+# 30, 40).  The sample is a clean image from --jpeg_dir, the degradation — a baseline JPEG round trip of the whole image — is made on the
+# device (rcot_amd/jpeg.py), the label is `single` again
+
+
+def jpeg_tasks(de_type: Sequence[str]) -> List[tuple]:
+    """the (name, quality) of every jpeg_q<Q> task of a --de_type list, in its order; SystemExit for a malformed name or quality"""
+    from .jpeg import parse_de_type
+    out = []
+    for t in de_type:
+        try:
+            q = parse_de_type(t)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        if q is not None:
+            out.append((t, q))
+    return out
+
+
+def jpeg_subsampling(args) -> int:
+    """--jpeg_subsampling 420 | 444 (default 420) as PIL's number"""
+    from .jpeg import SUBSAMPLING
+    v = str(getattr(args, "jpeg_subsampling", None) or "420")
+    if v not in SUBSAMPLING:
+        raise SystemExit(f"--jpeg_subsampling {v}: expected 420 or 444")
+    return SUBSAMPLING[v]
+
+
+def jpeg_dir_or_exit(args, de_type: str) -> str:
+    root = getattr(args, "jpeg_dir", None)
+    if root is None:
+        raise SystemExit(f"--de_type {de_type} needs --jpeg_dir DIR, a flat folder of clean images")
+    return root
 
 
 def crop_to_multiple(img: np.ndarray, base: int = 16) -> np.ndarray:
@@ -87,6 +121,11 @@ def build_sample_ids(args) -> List[dict]:
             root = sr_dir_or_exit(args, t)
             names = sorted(n for n in os.listdir(root) if os.path.isfile(os.path.join(root, n)))
             ids += [{"file": os.path.join(root, n), "de": DE_DICT["single"], "gt": None, "sr": scale} for n in names] * 5   # x5: `single`'s factor
+    for t, quality in jpeg_tasks(de_type):
+        root = jpeg_dir_or_exit(args, t)
+        sub = jpeg_subsampling(args)
+        names = sorted(n for n in os.listdir(root) if os.path.isfile(os.path.join(root, n)))
+        ids += [{"file": os.path.join(root, n), "de": DE_DICT["single"], "gt": None, "jpeg": (quality, sub)} for n in names] * 5
     return ids
 
 
@@ -165,6 +204,10 @@ class FolderLoader:
             from .resize import sr_degrade_u8
             assert getattr(self.be, "_plan", None) is None                  # loader launches stay outside recorded launch plans
             self.be.patch_prep(a, sr_degrade_u8(a, sid["sr"], self.be), y0, x0, P, mode, 0.0, nseed, deg_out, clean_out)
+        elif sid.get("jpeg"):  # compression artifacts: the WHOLE image makes the round trip, so a crop sees block borders at any phase
+            from .jpeg import jpeg_degrade_u8
+            assert getattr(self.be, "_plan", None) is None
+            self.be.patch_prep(a, jpeg_degrade_u8(a, *sid["jpeg"], self.be), y0, x0, P, mode, 0.0, nseed, deg_out, clean_out)
         elif gt is None:      # denoise_*: the file IS the clean image, the degradation is synthetic noise
             self.be.patch_prep(a, None, y0, x0, P, mode, NOISE_SIGMA[sid["de"]], nseed, deg_out, clean_out)
         else:
@@ -299,6 +342,16 @@ class FolderLoader:
                             from .resize import sr_degrade_u8
                             d = local[key] = cache.offer(key, sr_degrade_u8(a, sid["sr"], self.be))
                             cache.sr_degradations += 1
+                        rows.append((a, d, y0, x0, mode, 0.0, nseed))
+                    elif sid.get("jpeg"):
+                        key = (sid["file"], "jpeg", *sid["jpeg"])
+                        d = cache.lookup(key)
+                        if d is None:
+                            d = local.get(key)
+                        if d is None:
+                            from .jpeg import jpeg_degrade_u8
+                            d = local[key] = cache.offer(key, jpeg_degrade_u8(a, *sid["jpeg"], self.be))
+                            cache.jpeg_degradations += 1
                         rows.append((a, d, y0, x0, mode, 0.0, nseed))
                     elif gt is None:
                         rows.append((a, None, y0, x0, mode, NOISE_SIGMA[sid["de"]], nseed))

@@ -6,13 +6,16 @@ Keys
     (path, "crop16")            a decoded file after ``crop_to_multiple(..., 16)``
     (path, "crop16", "mod", s)  the HR image of an ``sr_x<s>`` sample after the further top-left crop to a multiple of ``s``
     (path, "sr", s)             its degraded twin, made ONCE by ``rcot_amd.resize.sr_degrade_u8``
+    (path, "jpeg", Q, S)        the twin of a ``jpeg_q<Q>`` sample (its clean image is the plain ``(path, "crop16")``), made ONCE by
+                                ``rcot_amd.jpeg.jpeg_degrade_u8`` with subsampling S (PIL's number: 2 = 4:2:0, 0 = 4:4:4)
 
 Budget: ``budget_bytes`` of image bytes.  An image that would take the total over the budget is not stored: the loader uses it as a
 transient tensor for the batch at hand (stream-ordered allocation keeps it alive until the launch has run) and meets it as a miss
 again next time.  There is no eviction and no reordering: what is resident depends only on the order of first touches, which the
 loader's seed fixes, so a run stays reproducible.
 
-Counters: ``images`` and ``bytes`` resident, ``hits`` and ``misses`` over every resolution of a key, ``sr_degradations`` made.
+Counters: ``images`` and ``bytes`` resident, ``hits`` and ``misses`` over every resolution of a key, ``sr_degradations`` and
+``jpeg_degradations`` made (the report names the latter once there is one).
 """
 from __future__ import annotations
 
@@ -25,7 +28,7 @@ class DeviceImageCache:
         self.device = backend.device
         self.budget = max(0, int(budget_bytes))
         self._store = {}
-        self.bytes = self.hits = self.misses = self.sr_degradations = 0
+        self.bytes = self.hits = self.misses = self.sr_degradations = self.jpeg_degradations = 0
 
     @property
     def images(self) -> int:
@@ -57,4 +60,5 @@ class DeviceImageCache:
 
     def report(self) -> str:
         return (f"data cache: {self.images} images, {self.bytes / 2 ** 20:.1f} MiB of {self.budget / 2 ** 30:g} GiB, {self.hits} hits, "
-                f"{self.misses} misses, {self.sr_degradations} sr degradations")
+                f"{self.misses} misses, {self.sr_degradations} sr degradations"
+                + (f", {self.jpeg_degradations} jpeg degradations" if self.jpeg_degradations else ""))

@@ -1494,6 +1494,27 @@ class HipBackend:
                                            taps.data_ptr(), K, self._st()), "rcot_resize_axis")
         return out
 
+    # ------------------------------------------------------------------ baseline JPEG round trip (csrc/jpeg.hip)
+    def jpeg_ws_bytes(self, h: int, w: int, subsampling: int) -> int:
+        """workspace bytes rcot_jpeg_roundtrip needs (0 for 4:4:4); RcotKernelError for a geometry it refuses"""
+        n = self.L.rcot_jpeg_ws_bytes(int(h), int(w), int(subsampling))
+        _lib.check(min(n, 0), "rcot_jpeg_ws_bytes")
+        return n
+
+    def jpeg_roundtrip(self, img_u8, quality: int, subsampling: int = 2, out=None, ws=None):
+        """img_u8 uint8 [h, w, 3] on the device -> uint8 [h, w, 3]: the image after a baseline JPEG round trip at ``quality`` (1 .. 100)
+        with ``subsampling`` 0 (4:4:4, one launch) or 2 (4:2:0, two launches through ``ws``, default the backend's workspace) — the bytes
+        Pillow on libjpeg-turbo holds after saving and loading it (rcot_jpeg_roundtrip)"""
+        self._u8_image(img_u8, "jpeg_roundtrip")
+        h, w, _ = img_u8.shape
+        if out is None:
+            out = torch.empty(h, w, 3, dtype=torch.uint8, device=self.device)
+        self._u8_image(out, "jpeg_roundtrip", h, w)
+        ws = self.ws if ws is None else ws
+        _lib.check(self.L.rcot_jpeg_roundtrip(img_u8.data_ptr(), out.data_ptr(), h, w, int(quality), int(subsampling), ws.data_ptr(),
+                                              ws.numel() * ws.element_size(), self._st()), "rcot_jpeg_roundtrip")
+        return out
+
     # ------------------------------------------------------------------ standard image-quality figures (csrc/quality.hip)
     WINDOWS = {"uniform7": 0, "gauss11": 1}
     SPACES = {"rgb": 0, "y": 1}

@@ -47,6 +47,13 @@ h x w LR images from ``--degset``, enlarges them by S and crops the target at th
 larger by S or more in either direction, are skipped with a message).  ``--savedeg DIR`` writes the 8-bit network input — the bicubic
 baseline every SR table starts with.  The padding, tiling, ensemble and metrics flags combine with these as before (``--color y
 --ssim_window gauss11`` is the protocol of SR tables); ``--sr_scale 0`` leaves everything as it was.
+
+Superset: ``--jpeg_q Q`` evaluates compression-artifact reduction (the CAR rows of restoration tables, Q = 10 / 20 / 30 / 40): the
+network's input is the whole target after a baseline JPEG round trip at quality Q made on the device (rcot_amd/jpeg.py,
+csrc/jpeg.hip: byte for byte what Pillow on libjpeg-turbo holds after saving and loading it; ``--jpeg_subsampling 420|444``, default
+420 as PIL's); ``--degset`` is not read.  ``--savedeg DIR`` writes that input, the "JPEG" baseline row.  The padding, tiling, ensemble
+and metrics flags combine with it as before; it is refused together with ``--sr_scale`` or ``--noise_sigma``; ``--jpeg_q 0`` (the
+default) leaves everything as it was.
 """
 from __future__ import annotations
 
@@ -94,6 +101,11 @@ parser.add_argument("--sr_scale", type=int, default=0,
 parser.add_argument("--sr_from", choices=["target", "lr"], default="target",
                     help="superset, with --sr_scale S: target = degrade the target (cropped at the top left to a multiple of S; --degset is "
                          "not read); lr = --degset holds the h x w low-resolution images, enlarged by S, the target is cropped to hS x wS")
+parser.add_argument("--jpeg_q", type=int, default=0,
+                    help="superset: compression-artifact reduction: the network's input is the target after a baseline JPEG round trip at "
+                         "this quality (1 .. 100) made on the device (rcot_amd/jpeg.py; --degset is not read); 0 = off, everything as before")
+parser.add_argument("--jpeg_subsampling", choices=["420", "444"], default="420",
+                    help="superset, with --jpeg_q: chroma subsampling of the round trip (420 = PIL's default)")
 parser.add_argument("--savedeg", default=None, type=str, help="superset: also write the 8-bit network input (with --sr_scale: the bicubic "
                                                              "baseline) as PNGs under this folder")
 
@@ -244,7 +256,9 @@ def _main_any_size(opt, net):
     tar_list = sorted(glob.glob(opt.tarset + "*"))
     S = opt.sr_scale
     sr_target = S > 0 and opt.sr_from == "target"
-    deg_list = tar_list if sr_target else sorted(glob.glob(opt.degset + "*"))       # (sr_from target: --degset is not read)
+    jpeg_q = opt.jpeg_q
+    # (sr_from target, jpeg_q: --degset is not read)
+    deg_list = tar_list if sr_target or jpeg_q > 0 else sorted(glob.glob(opt.degset + "*"))
     rng = np.random.default_rng(opt.seed)
     noisy = opt.noise_sigma is not None
     sizes, stats = [], []
@@ -257,6 +271,13 @@ def _main_any_size(opt, net):
             if pair is None:
                 continue
             deg, tar = pair
+        if jpeg_q > 0:
+            from .jpeg import SUBSAMPLING, jpeg_degrade_u8
+            sub = SUBSAMPLING[opt.jpeg_subsampling]
+            if sub == 2 and tar.shape[1] <= 4:
+                print(f"  skipped: target {tar.shape[0]} x {tar.shape[1]} is not wider than 4 pixels (4:2:0)")
+                continue
+            deg = jpeg_degrade_u8(torch.from_numpy(np.ascontiguousarray(tar)).to(be.device), jpeg_q, sub, be).cpu().numpy()
         if deg.shape != tar.shape:
             print(f"  skipped: degraded {deg.shape[0]} x {deg.shape[1]} and target {tar.shape[0]} x {tar.shape[1]} differ")
             continue
@@ -314,6 +335,10 @@ def main(argv=None):
     if opt.ssim_window == "box2" and opt.color == "y" and opt.metrics == "device":
         raise SystemExit("--ssim_window box2 with --color y (the reference's 2 x 2 map on the luma plane) is computed on the host only: "
                          "use --metrics folders, or --ssim_window uniform7 | gauss11")
+    if opt.jpeg_q < 0 or opt.jpeg_q > 100:
+        raise SystemExit(f"--jpeg_q {opt.jpeg_q}: the quality must be in 1 .. 100 (0 = off)")
+    if opt.jpeg_q > 0 and (opt.sr_scale > 0 or opt.noise_sigma is not None):
+        raise SystemExit("--jpeg_q makes the network's input from the target: it cannot be combined with --sr_scale or --noise_sigma")
     if not torch.cuda.is_available():
         raise SystemExit("No GPU found: rcot_amd.tester runs the HIP path only")
     if opt.sr_scale < 0 or opt.sr_scale == 1:
@@ -321,7 +346,7 @@ def main(argv=None):
     for d in (opt.save, opt.savetar, opt.saveres) + ((opt.savedeg,) if opt.savedeg else ()):
         os.makedirs(d, exist_ok=True)
     net, mult = load_network(opt.model)
-    if opt.pad != "none" or opt.metrics == "device" or opt.sr_scale > 0:
+    if opt.pad != "none" or opt.metrics == "device" or opt.sr_scale > 0 or opt.jpeg_q > 0:
         return _main_any_size(opt, net)
     deg_list, tar_list = sorted(glob.glob(opt.degset + "*")), sorted(glob.glob(opt.tarset + "*"))
     rng = np.random.default_rng(opt.seed)

@@ -52,6 +52,11 @@ parser.add_argument("--single_dir", type=str, default=None, help="(same for --de
 parser.add_argument("--sr_dir", type=str, default=None,
                     help="--de_type sr_x2 | sr_x3 | sr_x4: a flat folder of high-resolution images; the bicubic degradation (down by the "
                          "scale, 8 bits, up, 8 bits) is made on the device (rcot_amd/resize.py)")
+parser.add_argument("--jpeg_dir", type=str, default=None,
+                    help="--de_type jpeg_q<Q> (any Q in 1 .. 100; several may be mixed): a flat folder of clean images; the degradation, a "
+                         "baseline JPEG round trip of the whole image at quality Q, is made on the device (rcot_amd/jpeg.py)")
+parser.add_argument("--jpeg_subsampling", choices=["420", "444"], default="420",
+                    help="--de_type jpeg_q<Q>: chroma subsampling of the round trip (420 = PIL's default)")
 parser.add_argument("--seed", type=int, default=None, help="seed (the reference draws an unseeded random one)")
 parser.add_argument("--prec", choices=["fp32", "bf16x6", "bf16x3", "bf16x1"], default=os.environ.get("RCOT_GEMM_PREC", "fp32"),
                     help="arithmetic of the 1x1 MFMA products (include/rcot_hip.h RCOT_PREC_*; one default for HipBackend(), this CLI and "
@@ -67,7 +72,7 @@ parser.add_argument("--val_pad", choices=["none", "reflect", "replicate"], defau
                          "(rcot_amd/wholeimage.py); none = the reference's rule, images that are not multiples of 8 are skipped")
 parser.add_argument("--data_cache", choices=["off", "device"], default="off",
                     help="device: every training image is decoded once and stays on the device as uint8 (a super-resolution image with "
-                         "its degraded twin, made once); a batch is cut from the resident images in one launch "
+                         "its degraded twin, made once, and the JPEG twin of a jpeg_q<Q> image); a batch is cut from the resident images in one launch "
                          "(rcot_amd/imagecache.py).  The batches are those of `off`, bit for bit.  Ignored with --synthetic")
 parser.add_argument("--data_cache_gb", type=float, default=16.0,
                     help="--data_cache device: budget of image bytes per rank, in GiB; an image that does not fit is decoded again "
@@ -91,6 +96,19 @@ def check_sr_flags(o) -> None:
     if o.synthetic:
         raise SystemExit(f"--de_type {sr[0]} degrades whole images from --sr_dir: it cannot be combined with --synthetic")
     sr_dir_or_exit(o, sr[0])
+
+
+def check_jpeg_flags(o) -> None:
+    """the compression-artifact tasks jpeg_q<Q> read clean images from --jpeg_dir and degrade them on the device: a malformed name, a
+    quality outside 1 .. 100, a missing folder and --synthetic are refused up front"""
+    from .data import jpeg_dir_or_exit, jpeg_subsampling, jpeg_tasks
+    tasks = jpeg_tasks(o.de_type)
+    if not tasks:
+        return
+    if o.synthetic:
+        raise SystemExit(f"--de_type {tasks[0][0]} degrades whole images from --jpeg_dir: it cannot be combined with --synthetic")
+    jpeg_dir_or_exit(o, tasks[0][0])
+    jpeg_subsampling(o)
 
 
 def check_patch_size(P: int) -> int:
@@ -644,6 +662,7 @@ def main(argv=None):
     except ValueError as e:
         raise SystemExit(str(e))
     check_sr_flags(opt)
+    check_jpeg_flags(opt)
     # --backbone mprnet: with a GPU the older transport map runs on the HIP kernels (rcot_amd/mprnet_hip.py) through everything below —
     # data folders, data parallelism, validation, launch plans; without one (or with RCOT_MPRNET_STOCK=1) the stock-ops loop
     hip_mprnet = opt.backbone == "mprnet" and torch.cuda.is_available() and os.environ.get("RCOT_MPRNET_STOCK", "0") != "1"
