@@ -25,7 +25,7 @@ extern "C" {
 
 /* Bumped on EVERY signature change; returned by rcot_abi_version() (csrc/api.hip) and compared by the loader
  * (rcot_amd/lib.py ABI_VERSION, tests/test_abi.py) so that a stale prebuilt .so is refused, not mis-called. */
-#define RCOT_ABI_VERSION 32
+#define RCOT_ABI_VERSION 33
 
 /* Arithmetic of the MFMA products of the three GEMM-shaped entry points that take `prec` (rcot_gemm_kmajor,
  * rcot_conv1x1_wgrad, rcot_bmm_nt); operands and results are fp32 in memory either way.
@@ -556,6 +556,25 @@ int rcot_resize_axis(const float* src, float* dst, long planes, int H, int W, in
 int rcot_jpeg_ws_bytes(int H, int W, int subsampling);
 int rcot_jpeg_roundtrip(const unsigned char* src, unsigned char* dst, int H, int W, int quality, int subsampling, void* ws,
                         size_t ws_bytes, void* stream);
+
+/* ---- per-image PSF blur (csrc/blur.hip; rcot_amd/blur.py, the deblurring tasks blur_<spec> and the BD degradation sr_bd_x3) -----------
+ * src uint8 [H][W][3] (HWC, device) -> dst uint8 [H / step][W / step][3]: the K x K correlation (imfilter's orientation) of every channel
+ * with psf, a DEVICE int32 [K][K] array of weights >= 0 that sum to 2^22, sampled at (oy step + phase, ox step + phase):
+ *   acc = sum_i sum_j psf[i][j] src[by(y + i - r)][bx(x + j - r)],  r = (K - 1) / 2,  out = (acc + 2^21) >> 22
+ * The rule is written out in the header comment of csrc/blur.hip.
+ *   border  0 replicate (clamp), 1 mirror (reflection without the edge sample, period 2 (n - 1); n = 1 maps to 0), 2 wrap (modulo n);
+ *           each valid at any distance outside the image
+ *   step, phase  step 1, phase 0: the plain blur; step 3, phase 1: every third pixel from the centre of each 3 x 3 cell.  Only the sampled
+ *           outputs are computed.
+ *   One launch, no workspace, no atomics, any H, W >= 1 and any alignment of src and dst; bitwise reproducible.
+ *   The weights are the caller's contract (rcot_amd/blur.py checks them on the host before the upload).  For anything else a product
+ *   takes the low 24 bits of its weight, the sum wraps modulo 2^32 and the low 8 bits of the shifted sum are stored; every image index
+ *   goes through the border map, so no PSF can make the kernels read outside the image.
+ *  RCOT_EINVAL (nothing is launched, dst is untouched): a null pointer; H or W < 1; K even or < 1; border outside {0, 1, 2}; step < 1;
+ *  phase outside [0, step); H or W not a multiple of step.
+ *  RCOT_EUNSUPPORTED (the same): K > 63; an image of 2^31 bytes or more. */
+int rcot_blur_u8(const unsigned char* src, unsigned char* dst, int H, int W, const int* psf, int K, int border, int step, int phase,
+                 void* stream);
 
 #ifdef __cplusplus
 }

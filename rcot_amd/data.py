@@ -5,16 +5,17 @@ same replication factors, same clean/ground-truth naming rules :198-213) and PIL
 image to ONE device kernel (``rcot_patch_prep``) that crops, applies the dihedral augmentation, adds the Gaussian noise of
 the denoise_* tasks and converts to CHW float (rcot_amd/csrc/dataprep.hip).  The sr_x2 / sr_x3 / sr_x4 tasks (``--sr_dir``) degrade
 the whole HR image on the device first (rcot_amd/resize.py) and hand both images to the same kernel; the jpeg_q<Q> tasks (``--jpeg_dir``)
-do the same with a baseline JPEG round trip (rcot_amd/jpeg.py).  The reference does those steps with
-PIL/numpy on the host at ``num_workers=0`` (trainer.py:32,134).
+do the same with a baseline JPEG round trip (rcot_amd/jpeg.py), the blur_<spec> tasks (``--blur_dir``) and sr_bd_x3 with a PSF blur
+(rcot_amd/blur.py).  The reference does those steps with PIL/numpy on the host at ``num_workers=0`` (trainer.py:32,134).
 
 ``FolderLoader(..., cache=DeviceImageCache(...))`` (the trainer's ``--data_cache device``, rcot_amd/imagecache.py) keeps every decoded
 image — and the degraded twin of an HR image — on the device after its first use and cuts a whole batch from the resident images in ONE
 launch (``rcot_patch_prep_batch``); the batches are the uncached loader's, bit for bit.
 
 Randomness: the reference leaves python's ``random`` and numpy unseeded; here every draw (epoch
-shuffle, crop origin, augmentation mode 1..7, noise seed) comes from one ``random.Random(seed, epoch)`` stream indexed by
-the GLOBAL sample position, so a run is reproducible and the union of the ranks' shards does not depend on the world size.
+shuffle, crop origin, augmentation mode 1..7, noise seed, then the angle of a blur_m<L> sample) comes from one
+``random.Random(seed, epoch)`` stream indexed by the GLOBAL sample position, so a run is reproducible and the union of the ranks'
+shards does not depend on the world size.
 """
 from __future__ import annotations
 
@@ -35,6 +36,41 @@ SR_SCALE = {"sr_x2": 2, "sr_x3": 3, "sr_x4": 4}
 # superset: compression-artifact reduction, --de_type jpeg_q<Q> for any Q in 1 .. 100 (the CAR rows of restoration tables use 10, 20,
 # 30, 40).  The sample is a clean image from --jpeg_dir, the degradation — a baseline JPEG round trip of the whole image — is made on the
 # device (rcot_amd/jpeg.py), the label is `single` again
+# superset: deblurring from sharp images alone, --de_type blur_<spec> (rcot_amd/blur.py's PSF grammar: blur_g1.6, blur_g2k15, blur_m15a30,
+# blur_m15).  The sample is a sharp image from --blur_dir, the WHOLE image is blurred on the device, the label is the reference's `deblur`.
+# A motion PSF without an angle draws whole degrees per sample.  sr_bd_x3 is the "BD" row of super-resolution tables (Gaussian 7 x 7,
+# sigma 1.6, every third pixel, bicubic x3 back): an HR image from --sr_dir, decoded as sr_x3 decodes it, the label `single`
+SR_BD = "sr_bd_x3"
+
+
+def blur_tasks(de_type: Sequence[str]) -> List[tuple]:
+    """the (name, PSF spec) of every blur_<spec> task of a --de_type list, in its order; SystemExit for a malformed name"""
+    from .blur import parse_de_type
+    out = []
+    for t in de_type:
+        try:
+            spec = parse_de_type(t)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        if spec is not None:
+            out.append((t, spec))
+    return out
+
+
+def blur_border(args) -> str:
+    """--blur_border replicate | mirror | wrap (default replicate)"""
+    from .blur import BORDERS
+    v = str(getattr(args, "blur_border", None) or "replicate")
+    if v not in BORDERS:
+        raise SystemExit(f"--blur_border {v}: expected replicate, mirror or wrap")
+    return v
+
+
+def blur_dir_or_exit(args, de_type: str) -> str:
+    root = getattr(args, "blur_dir", None)
+    if root is None:
+        raise SystemExit(f"--de_type {de_type} needs --blur_dir DIR, a flat folder of sharp images")
+    return root
 
 
 def jpeg_tasks(de_type: Sequence[str]) -> List[tuple]:
@@ -126,6 +162,15 @@ def build_sample_ids(args) -> List[dict]:
         sub = jpeg_subsampling(args)
         names = sorted(n for n in os.listdir(root) if os.path.isfile(os.path.join(root, n)))
         ids += [{"file": os.path.join(root, n), "de": DE_DICT["single"], "gt": None, "jpeg": (quality, sub)} for n in names] * 5
+    for t, spec in blur_tasks(de_type):
+        root = blur_dir_or_exit(args, t)
+        border = blur_border(args)
+        names = sorted(n for n in os.listdir(root) if os.path.isfile(os.path.join(root, n)))
+        ids += [{"file": os.path.join(root, n), "de": DE_DICT["deblur"], "gt": None, "blur": (spec, border)} for n in names] * 5
+    if SR_BD in de_type:                                                    # "sr": 3 — the decode and the cached HR image of sr_x3
+        root = sr_dir_or_exit(args, SR_BD)
+        names = sorted(n for n in os.listdir(root) if os.path.isfile(os.path.join(root, n)))
+        ids += [{"file": os.path.join(root, n), "de": DE_DICT["single"], "gt": None, "sr": 3, "bd": True} for n in names] * 5
     return ids
 
 
@@ -200,7 +245,14 @@ class FolderLoader:
         nseed = rng.getrandbits(63)
         dev = self.be.device
         a = torch.from_numpy(img).to(dev, non_blocking=True)
-        if sid.get("sr"):     # super-resolution: the file is the HR image; the WHOLE image is degraded, so the crop sees real neighbours
+        if sid.get("bd"):     # super-resolution, BD protocol: blurred, sampled and enlarged again as a whole
+            from .blur import bd_degrade_u8
+            assert getattr(self.be, "_plan", None) is None
+            self.be.patch_prep(a, bd_degrade_u8(a, self.be), y0, x0, P, mode, 0.0, nseed, deg_out, clean_out)
+        elif sid.get("blur"):  # deblurring: the WHOLE image is blurred, so a patch sees real neighbours and no border rule inside the image
+            assert getattr(self.be, "_plan", None) is None
+            self.be.patch_prep(a, self._blurred(rng, sid, a), y0, x0, P, mode, 0.0, nseed, deg_out, clean_out)
+        elif sid.get("sr"):   # super-resolution: the file is the HR image; the WHOLE image is degraded, so the crop sees real neighbours
             from .resize import sr_degrade_u8
             assert getattr(self.be, "_plan", None) is None                  # loader launches stay outside recorded launch plans
             self.be.patch_prep(a, sr_degrade_u8(a, sid["sr"], self.be), y0, x0, P, mode, 0.0, nseed, deg_out, clean_out)
@@ -213,6 +265,14 @@ class FolderLoader:
         else:
             g = torch.from_numpy(gt).to(dev, non_blocking=True)
             self.be.patch_prep(g, a, y0, x0, P, mode, 0.0, nseed, deg_out, clean_out)
+
+    def _blurred(self, rng: random.Random, sid: dict, a):
+        """the blurred twin of the device image ``a`` of a blur_<spec> sample; a motion PSF without an angle draws whole degrees from the
+        sample's stream — AFTER the crop, mode and noise-seed draws, which therefore are those of every other task"""
+        from .blur import blur_degrade_u8, needs_angle, psf_q_of
+        spec, border = sid["blur"]
+        angle = rng.randint(0, 179) if needs_angle(spec) else None
+        return blur_degrade_u8(a, psf_q_of(spec, angle), border, self.be)
 
     def __iter__(self):
         if self.cache is not None:
@@ -333,7 +393,30 @@ class FolderLoader:
                     y0, x0 = rng.randint(0, H - P), rng.randint(0, W - P)   # the draws of _sample, in its order
                     mode = rng.randint(1, 7)
                     nseed = rng.getrandbits(63)
-                    if sid.get("sr"):
+                    if sid.get("bd"):
+                        key = (sid["file"], "bd", 3)
+                        d = cache.lookup(key)
+                        if d is None:
+                            d = local.get(key)
+                        if d is None:
+                            from .blur import bd_degrade_u8
+                            d = local[key] = cache.offer(key, bd_degrade_u8(a, self.be))
+                            cache.blur_degradations += 1
+                        rows.append((a, d, y0, x0, mode, 0.0, nseed))
+                    elif sid.get("blur"):
+                        from .blur import needs_angle
+                        if needs_angle(sid["blur"][0]):                    # an angle per sample: the twin is made per sample, not kept
+                            d = self._blurred(rng, sid, a)
+                        else:
+                            key = (sid["file"], "blur", *sid["blur"])
+                            d = cache.lookup(key)
+                            if d is None:
+                                d = local.get(key)
+                            if d is None:
+                                d = local[key] = cache.offer(key, self._blurred(rng, sid, a))
+                                cache.blur_degradations += 1
+                        rows.append((a, d, y0, x0, mode, 0.0, nseed))
+                    elif sid.get("sr"):
                         key = (sid["file"], "sr", sid["sr"])
                         d = cache.lookup(key)
                         if d is None:

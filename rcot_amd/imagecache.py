@@ -8,6 +8,10 @@ Keys
     (path, "sr", s)             its degraded twin, made ONCE by ``rcot_amd.resize.sr_degrade_u8``
     (path, "jpeg", Q, S)        the twin of a ``jpeg_q<Q>`` sample (its clean image is the plain ``(path, "crop16")``), made ONCE by
                                 ``rcot_amd.jpeg.jpeg_degrade_u8`` with subsampling S (PIL's number: 2 = 4:2:0, 0 = 4:4:4)
+    (path, "blur", spec, border) the twin of a ``blur_<spec>`` sample whose PSF is fixed (clean image: ``(path, "crop16")``), made ONCE by
+                                ``rcot_amd.blur.blur_degrade_u8``; a motion PSF that draws its angle per sample has no resident twin
+    (path, "bd", 3)             the twin of an ``sr_bd_x3`` sample (HR image: ``(path, "crop16", "mod", 3)``, shared with ``sr_x3``),
+                                made ONCE by ``rcot_amd.blur.bd_degrade_u8``
 
 Budget: ``budget_bytes`` of image bytes.  An image that would take the total over the budget is not stored: the loader uses it as a
 transient tensor for the batch at hand (stream-ordered allocation keeps it alive until the launch has run) and meets it as a miss
@@ -15,7 +19,8 @@ again next time.  There is no eviction and no reordering: what is resident depen
 loader's seed fixes, so a run stays reproducible.
 
 Counters: ``images`` and ``bytes`` resident, ``hits`` and ``misses`` over every resolution of a key, ``sr_degradations`` and
-``jpeg_degradations`` made (the report names the latter once there is one).
+``jpeg_degradations`` made (the report names the latter once there is one), ``blur_degradations``: whole-image blurs kept, BD included
+(named last, once there is one).
 """
 from __future__ import annotations
 
@@ -28,7 +33,7 @@ class DeviceImageCache:
         self.device = backend.device
         self.budget = max(0, int(budget_bytes))
         self._store = {}
-        self.bytes = self.hits = self.misses = self.sr_degradations = self.jpeg_degradations = 0
+        self.bytes = self.hits = self.misses = self.sr_degradations = self.jpeg_degradations = self.blur_degradations = 0
 
     @property
     def images(self) -> int:
@@ -61,4 +66,5 @@ class DeviceImageCache:
     def report(self) -> str:
         return (f"data cache: {self.images} images, {self.bytes / 2 ** 20:.1f} MiB of {self.budget / 2 ** 30:g} GiB, {self.hits} hits, "
                 f"{self.misses} misses, {self.sr_degradations} sr degradations"
-                + (f", {self.jpeg_degradations} jpeg degradations" if self.jpeg_degradations else ""))
+                + (f", {self.jpeg_degradations} jpeg degradations" if self.jpeg_degradations else "")
+                + (f", {self.blur_degradations} blur degradations" if self.blur_degradations else ""))

@@ -1515,6 +1515,26 @@ class HipBackend:
                                               ws.numel() * ws.element_size(), self._st()), "rcot_jpeg_roundtrip")
         return out
 
+    # ------------------------------------------------------------------ per-image PSF blur (csrc/blur.hip)
+    def blur_u8(self, img_u8, psf_dev, border: int, step: int = 1, phase: int = 0, out=None):
+        """img_u8 uint8 [h, w, 3] on the device -> uint8 [h / step, w / step, 3]: every channel correlated with ``psf_dev`` (int32 [K, K]
+        on the device, K odd, weights >= 0 that sum to 2^22: rcot_amd.blur.device_psf) under the border rule ``border`` (0 replicate,
+        1 mirror, 2 wrap), sampled at (oy step + phase, ox step + phase) (rcot_blur_u8: one launch, no workspace)"""
+        self._u8_image(img_u8, "blur_u8")
+        if psf_dev.dtype != torch.int32 or not psf_dev.is_cuda or not psf_dev.is_contiguous() or psf_dev.dim() != 2 \
+                or psf_dev.shape[0] != psf_dev.shape[1]:
+            raise _lib.RcotKernelError("blur_u8: the PSF must be a contiguous int32 [K, K] tensor on the HIP device")
+        h, w, _ = img_u8.shape
+        step, phase = int(step), int(phase)
+        if step < 1 or h % step or w % step:
+            raise _lib.RcotKernelError(f"blur_u8: invalid argument: {h} x {w} pixels are not multiples of the step {step}")
+        if out is None:
+            out = torch.empty(h // step, w // step, 3, dtype=torch.uint8, device=self.device)
+        self._u8_image(out, "blur_u8", h // step, w // step)
+        _lib.check(self.L.rcot_blur_u8(img_u8.data_ptr(), out.data_ptr(), h, w, psf_dev.data_ptr(), int(psf_dev.shape[0]), int(border),
+                                       step, phase, self._st()), "rcot_blur_u8")
+        return out
+
     # ------------------------------------------------------------------ standard image-quality figures (csrc/quality.hip)
     WINDOWS = {"uniform7": 0, "gauss11": 1}
     SPACES = {"rgb": 0, "y": 1}

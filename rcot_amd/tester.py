@@ -54,6 +54,13 @@ csrc/jpeg.hip: byte for byte what Pillow on libjpeg-turbo holds after saving and
 420 as PIL's); ``--degset`` is not read.  ``--savedeg DIR`` writes that input, the "JPEG" baseline row.  The padding, tiling, ensemble
 and metrics flags combine with it as before; it is refused together with ``--sr_scale`` or ``--noise_sigma``; ``--jpeg_q 0`` (the
 default) leaves everything as it was.
+
+Superset: ``--blur SPEC`` evaluates deblurring from sharp images alone: the network's input is the whole target blurred on the device by
+the PSF of the spec (rcot_amd/blur.py's grammar: g1.6, g2k15, a4x1r30, m15a30; csrc/blur.hip) under ``--blur_border
+replicate|mirror|wrap``; ``--degset`` is not read.  ``--savedeg DIR`` writes that input, the "blurred" baseline row.  It is refused
+together with ``--sr_scale``, ``--jpeg_q`` or ``--noise_sigma``.  ``--sr_degradation bd`` (with ``--sr_scale 3 --sr_from target`` only)
+replaces the bicubic shrink of the SR input by the BD protocol — Gaussian 7 x 7, sigma 1.6, every third pixel — before the same bicubic
+enlargement; the default ``bicubic`` is the path above.  With neither flag everything runs as before.
 """
 from __future__ import annotations
 
@@ -106,6 +113,14 @@ parser.add_argument("--jpeg_q", type=int, default=0,
                          "this quality (1 .. 100) made on the device (rcot_amd/jpeg.py; --degset is not read); 0 = off, everything as before")
 parser.add_argument("--jpeg_subsampling", choices=["420", "444"], default="420",
                     help="superset, with --jpeg_q: chroma subsampling of the round trip (420 = PIL's default)")
+parser.add_argument("--blur", default=None, type=str,
+                    help="superset: deblurring: the network's input is the target blurred on the device by this PSF spec (rcot_amd/blur.py: "
+                         "g1.6, g2k15, a4x1r30, m15a30; --degset is not read); off by default, everything as before")
+parser.add_argument("--blur_border", choices=["replicate", "mirror", "wrap"], default="replicate",
+                    help="superset, with --blur: the border rule of the blur")
+parser.add_argument("--sr_degradation", choices=["bicubic", "bd"], default="bicubic",
+                    help="superset, with --sr_scale 3 --sr_from target: bd = Gaussian 7 x 7 sigma 1.6 and every third pixel instead of the "
+                         "bicubic shrink (the BD rows of SR tables); bicubic = the path as before")
 parser.add_argument("--savedeg", default=None, type=str, help="superset: also write the 8-bit network input (with --sr_scale: the bicubic "
                                                              "baseline) as PNGs under this folder")
 
@@ -222,11 +237,12 @@ def _report(psnr, ssim, pmax, smax, pmin, smin, done, ssim_window="box2", color=
                 ssim_window=ssim_window, color=color)
 
 
-def _sr_pair(deg: np.ndarray, tar: np.ndarray, S: int, from_target: bool, be):
+def _sr_pair(deg: np.ndarray, tar: np.ndarray, S: int, from_target: bool, be, bd: bool = False):
     """``--sr_scale S``: (network input, target) as uint8 [H, W, 3] arrays of one size, or None (with a message) for a pair that is
     skipped.  from_target: the target is cropped at the top left to a multiple of S and degraded (down, 8 bits, up, 8 bits).  Else
     ``deg`` is the h x w LR image: it is enlarged to hS x wS, and the target is cropped to that at the top left — it may be larger by
-    less than S in either direction (what the crop to a multiple of S removed when the LR image was made)."""
+    less than S in either direction (what the crop to a multiple of S removed when the LR image was made).  ``bd`` (from_target, S = 3):
+    the degradation is rcot_amd.blur.bd_degrade_u8."""
     from .resize import sr_degrade_u8, sr_upscale_u8
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(be.device)
     if from_target:
@@ -235,6 +251,9 @@ def _sr_pair(deg: np.ndarray, tar: np.ndarray, S: int, from_target: bool, be):
             print(f"  skipped: target {tar.shape[0]} x {tar.shape[1]} is smaller than the scale factor {S}")
             return None
         tar = np.ascontiguousarray(tar[:H, :W])
+        if bd:
+            from .blur import bd_degrade_u8
+            return bd_degrade_u8(up(tar), be).cpu().numpy(), tar
         return sr_degrade_u8(up(tar), S, be).cpu().numpy(), tar
     H, W = deg.shape[0] * S, deg.shape[1] * S
     if tar.shape[0] < H or tar.shape[1] < W or tar.shape[0] - H >= S or tar.shape[1] - W >= S:
@@ -257,8 +276,12 @@ def _main_any_size(opt, net):
     S = opt.sr_scale
     sr_target = S > 0 and opt.sr_from == "target"
     jpeg_q = opt.jpeg_q
-    # (sr_from target, jpeg_q: --degset is not read)
-    deg_list = tar_list if sr_target or jpeg_q > 0 else sorted(glob.glob(opt.degset + "*"))
+    blur_q = None
+    if opt.blur is not None:
+        from .blur import blur_degrade_u8, psf_q_of
+        blur_q = psf_q_of(opt.blur)
+    # (sr_from target, jpeg_q, blur: --degset is not read)
+    deg_list = tar_list if sr_target or jpeg_q > 0 or blur_q is not None else sorted(glob.glob(opt.degset + "*"))
     rng = np.random.default_rng(opt.seed)
     noisy = opt.noise_sigma is not None
     sizes, stats = [], []
@@ -267,7 +290,7 @@ def _main_any_size(opt, net):
         print("Processing ", deg_name)
         deg, tar = np.array(Image.open(deg_name).convert("RGB")), np.array(Image.open(tar_name).convert("RGB"))
         if S > 0:
-            pair = _sr_pair(deg, tar, S, sr_target, be)
+            pair = _sr_pair(deg, tar, S, sr_target, be, opt.sr_degradation == "bd")
             if pair is None:
                 continue
             deg, tar = pair
@@ -278,6 +301,8 @@ def _main_any_size(opt, net):
                 print(f"  skipped: target {tar.shape[0]} x {tar.shape[1]} is not wider than 4 pixels (4:2:0)")
                 continue
             deg = jpeg_degrade_u8(torch.from_numpy(np.ascontiguousarray(tar)).to(be.device), jpeg_q, sub, be).cpu().numpy()
+        if blur_q is not None:
+            deg = blur_degrade_u8(torch.from_numpy(np.ascontiguousarray(tar)).to(be.device), blur_q, opt.blur_border, be).cpu().numpy()
         if deg.shape != tar.shape:
             print(f"  skipped: degraded {deg.shape[0]} x {deg.shape[1]} and target {tar.shape[0]} x {tar.shape[1]} differ")
             continue
@@ -339,6 +364,19 @@ def main(argv=None):
         raise SystemExit(f"--jpeg_q {opt.jpeg_q}: the quality must be in 1 .. 100 (0 = off)")
     if opt.jpeg_q > 0 and (opt.sr_scale > 0 or opt.noise_sigma is not None):
         raise SystemExit("--jpeg_q makes the network's input from the target: it cannot be combined with --sr_scale or --noise_sigma")
+    if opt.blur is not None:
+        from .blur import GRAMMAR, needs_angle, parse_psf
+        if opt.sr_scale > 0 or opt.jpeg_q > 0 or opt.noise_sigma is not None:
+            raise SystemExit("--blur makes the network's input from the target: it cannot be combined with --sr_scale, --jpeg_q or "
+                             "--noise_sigma")
+        try:
+            parse_psf(opt.blur)
+            if needs_angle(opt.blur):
+                raise ValueError(f"PSF spec {opt.blur!r}: an evaluation blurs with one fixed angle, m<L>a<deg>; {GRAMMAR}")
+        except ValueError as e:
+            raise SystemExit(f"--blur: {e}")
+    if opt.sr_degradation == "bd" and (opt.sr_scale != 3 or opt.sr_from != "target"):
+        raise SystemExit("--sr_degradation bd is the BD protocol of scale 3 made from the target: it needs --sr_scale 3 --sr_from target")
     if not torch.cuda.is_available():
         raise SystemExit("No GPU found: rcot_amd.tester runs the HIP path only")
     if opt.sr_scale < 0 or opt.sr_scale == 1:
@@ -346,7 +384,7 @@ def main(argv=None):
     for d in (opt.save, opt.savetar, opt.saveres) + ((opt.savedeg,) if opt.savedeg else ()):
         os.makedirs(d, exist_ok=True)
     net, mult = load_network(opt.model)
-    if opt.pad != "none" or opt.metrics == "device" or opt.sr_scale > 0 or opt.jpeg_q > 0:
+    if opt.pad != "none" or opt.metrics == "device" or opt.sr_scale > 0 or opt.jpeg_q > 0 or opt.blur is not None:
         return _main_any_size(opt, net)
     deg_list, tar_list = sorted(glob.glob(opt.degset + "*")), sorted(glob.glob(opt.tarset + "*"))
     rng = np.random.default_rng(opt.seed)

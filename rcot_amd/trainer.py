@@ -57,6 +57,11 @@ parser.add_argument("--jpeg_dir", type=str, default=None,
                          "baseline JPEG round trip of the whole image at quality Q, is made on the device (rcot_amd/jpeg.py)")
 parser.add_argument("--jpeg_subsampling", choices=["420", "444"], default="420",
                     help="--de_type jpeg_q<Q>: chroma subsampling of the round trip (420 = PIL's default)")
+parser.add_argument("--blur_dir", type=str, default=None,
+                    help="--de_type blur_<spec> (rcot_amd/blur.py's PSF grammar: blur_g1.6, blur_g2k15, blur_m15a30; blur_m15 draws an angle "
+                         "per sample; several may be mixed): a flat folder of sharp images; the whole image is blurred on the device")
+parser.add_argument("--blur_border", choices=["replicate", "mirror", "wrap"], default="replicate",
+                    help="--de_type blur_<spec>: the border rule of the blur")
 parser.add_argument("--seed", type=int, default=None, help="seed (the reference draws an unseeded random one)")
 parser.add_argument("--prec", choices=["fp32", "bf16x6", "bf16x3", "bf16x1"], default=os.environ.get("RCOT_GEMM_PREC", "fp32"),
                     help="arithmetic of the 1x1 MFMA products (include/rcot_hip.h RCOT_PREC_*; one default for HipBackend(), this CLI and "
@@ -72,7 +77,7 @@ parser.add_argument("--val_pad", choices=["none", "reflect", "replicate"], defau
                          "(rcot_amd/wholeimage.py); none = the reference's rule, images that are not multiples of 8 are skipped")
 parser.add_argument("--data_cache", choices=["off", "device"], default="off",
                     help="device: every training image is decoded once and stays on the device as uint8 (a super-resolution image with "
-                         "its degraded twin, made once, and the JPEG twin of a jpeg_q<Q> image); a batch is cut from the resident images in one launch "
+                         "its degraded twin, made once, the JPEG twin of a jpeg_q<Q> image and the blurred twin of a blur_<spec> image with a fixed PSF); a batch is cut from the resident images in one launch "
                          "(rcot_amd/imagecache.py).  The batches are those of `off`, bit for bit.  Ignored with --synthetic")
 parser.add_argument("--data_cache_gb", type=float, default=16.0,
                     help="--data_cache device: budget of image bytes per rank, in GiB; an image that does not fit is decoded again "
@@ -109,6 +114,24 @@ def check_jpeg_flags(o) -> None:
         raise SystemExit(f"--de_type {tasks[0][0]} degrades whole images from --jpeg_dir: it cannot be combined with --synthetic")
     jpeg_dir_or_exit(o, tasks[0][0])
     jpeg_subsampling(o)
+
+
+def check_blur_flags(o) -> None:
+    """the deblurring tasks blur_<spec> read sharp images from --blur_dir, sr_bd_x3 HR images from --sr_dir, and both blur them on the
+    device: a malformed name, a missing folder and --synthetic are refused up front"""
+    from .data import SR_BD, blur_border, blur_dir_or_exit, blur_tasks, sr_dir_or_exit
+    tasks = blur_tasks(o.de_type)
+    bd = SR_BD in o.de_type
+    if not tasks and not bd:
+        return
+    if o.synthetic:
+        name, flag = (tasks[0][0], "--blur_dir") if tasks else (SR_BD, "--sr_dir")
+        raise SystemExit(f"--de_type {name} degrades whole images from {flag}: it cannot be combined with --synthetic")
+    if tasks:
+        blur_dir_or_exit(o, tasks[0][0])
+        blur_border(o)
+    if bd:
+        sr_dir_or_exit(o, SR_BD)
 
 
 def check_patch_size(P: int) -> int:
@@ -663,6 +686,7 @@ def main(argv=None):
         raise SystemExit(str(e))
     check_sr_flags(opt)
     check_jpeg_flags(opt)
+    check_blur_flags(opt)
     # --backbone mprnet: with a GPU the older transport map runs on the HIP kernels (rcot_amd/mprnet_hip.py) through everything below —
     # data folders, data parallelism, validation, launch plans; without one (or with RCOT_MPRNET_STOCK=1) the stock-ops loop
     hip_mprnet = opt.backbone == "mprnet" and torch.cuda.is_available() and os.environ.get("RCOT_MPRNET_STOCK", "0") != "1"
