@@ -92,7 +92,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--skip-train", action="store_true")
     ap.add_argument("--only", default="", help="comma list of sections to (re)generate: blocks,convs,tnet,tnet128,fnet,"
-                    "otcost,train,train128,traj,ckpt,itergrads,gpufx,init,mprnet,mprnetfx,data,blocks8 (default: the round-1 set blocks,convs,tnet,fnet,otcost,train)")
+                    "otcost,train,train128,traj,ckpt,itergrads,gpufx,init,mprnet,mprnetfx,data,blocks8,wholeimage (default: the round-1 set blocks,convs,tnet,fnet,otcost,train)")
     args = ap.parse_args()
     only = set(args.only.split(",")) if args.only else {"blocks", "convs", "tnet", "fnet", "otcost", "train"}
     if args.skip_train:
@@ -926,6 +926,25 @@ def main():
                       f"({len(ref_ids)} ids incl. the x5 / x360 / x5 replication and the unlisted-file rule == build_sample_ids as a "
                       "multiset, asserted here); the rain / haze ground-truth naming rules; one verbatim __getitem__ per paired task "
                       "(derain, dehaze) with its crop origin and augmentation mode recorded")
+
+    # ---------------------------------------------------------------- whole image at a real size class (tests/test_inference_shapes_gpu.py)
+    if "wholeimage" in only:
+        # 161 x 241, reflect-padded at the bottom / right to 168 x 248 as rcot_amd.wholeimage pads it: planes of 84 x 124 = 64 * 651
+        # (N % 128 = 64), 42 x 62 and 21 x 31 pixels (the last width-padded to 21 x 32 by T_net._lat_pad); the cropped output is stored
+        h, w, seed = 161, 241, 905
+        refT.load_state_dict(to_t(P.seeded_params(P.tnet_param_shapes(), 11, "T")))
+        x = seeded_tensor(seed, (1, 3, h, w), lo=0.0, hi=1.0)
+        xp = torch.nn.functional.pad(x, (0, 248 - w, 0, 168 - h), mode="reflect")
+        with torch.no_grad():
+            y = refT(xp)[:, :, :h, :w].contiguous()
+            yo = O.tnet_forward(to_t(P.seeded_params(P.tnet_param_shapes(), 11, "T")), xp, True)[:, :, :h, :w]
+            yd = O.tnet_forward({k: v.double() for k, v in to_t(P.seeded_params(P.tnet_param_shapes(), 11, "T")).items()}, xp.double(),
+                                True)[:, :, :h, :w]
+        e_or, e_f32 = relerr(yo, y), relerr(y, yd)
+        assert e_or < 1e-4, e_or
+        np.savez_compressed(os.path.join(GOLD, "wholeimage.npz"), cfg=np.array([1, h, w, seed, 11]), y=y.numpy().astype(np.float32))
+        report.append(f"T_net(decoder=True) on a {h} x {w} image reflect-padded to 168 x 248 (seed {seed}): reference output stored cropped "
+                      f"(wholeimage.npz); oracle in float32 vs reference {e_or:.2e}; reference (float32) vs oracle in float64 {e_f32:.2e}")
 
     mode = "a" if args.only else "w"
     with open(os.path.join(ROOT, "oracle", "PINNED.md"), mode) as f:

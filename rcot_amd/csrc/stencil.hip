@@ -637,6 +637,7 @@ int rcot_dwconv3x3(const float* x, const float* w, float* y, int B, int C, int H
     if ((W & 3) || (H & 3)) {
         if (flip) return RCOT_EINVAL;                      // the data gradient is only needed at training patch sizes
         const long total = (long)B * C * H * W;
+        note_kernel("dwconv_any_kernel");
         RCOT_LAUNCH(dwconv_any_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, w, y, total, C, H, W);
         RCOT_LAUNCH_CHECK();
         return RCOT_OK;
@@ -656,6 +657,7 @@ int rcot_gdfn_gate_fwd(const float* p, const float* w, float* g, int B, int hid,
     if (!p || !w || !g || B <= 0 || hid <= 0 || H <= 0 || W <= 0) return RCOT_EINVAL;
     if ((W & 3) || (H & 3)) {
         const long total = (long)B * hid * H * W;
+        note_kernel("gate_fwd_any_kernel");
         RCOT_LAUNCH(gate_fwd_any_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, p, w, g, total, hid, H, W);
         RCOT_LAUNCH_CHECK();
         return RCOT_OK;
@@ -664,7 +666,9 @@ int rcot_gdfn_gate_fwd(const float* p, const float* w, float* g, int B, int hid,
     const long nq = (long)B * hid * (H >> 2) * (W >> 2);
     // the neighbour-lane form of the patch loads (all twelve rows of both planes requested before the first lane shift; with the
     // loads inside per-row `if` blocks it measured SLOWER than the scalar-halo form, 33.8 vs 30.8 us)
-    if (nb_lanes_ok(W))
+    const bool nb = nb_lanes_ok(W);
+    note_kernel("gate_fwd_kernel<%s>", tf(nb));
+    if (nb)
         RCOT_LAUNCH(gate_fwd_kernel<true>, dim3(cdiv(nq, 256)), dim3(256), 0, (hipStream_t)stream, p, w, g, nq, hid, H, W);
     else
         RCOT_LAUNCH(gate_fwd_kernel<false>, dim3(cdiv(nq, 256)), dim3(256), 0, (hipStream_t)stream, p, w, g, nq, hid, H, W);
