@@ -25,7 +25,7 @@ extern "C" {
 
 /* Bumped on EVERY signature change; returned by rcot_abi_version() (csrc/api.hip) and compared by the loader
  * (rcot_amd/lib.py ABI_VERSION, tests/test_abi.py) so that a stale prebuilt .so is refused, not mis-called. */
-#define RCOT_ABI_VERSION 33
+#define RCOT_ABI_VERSION 34
 
 /* Arithmetic of the MFMA products of the three GEMM-shaped entry points that take `prec` (rcot_gemm_kmajor,
  * rcot_conv1x1_wgrad, rcot_bmm_nt); operands and results are fp32 in memory either way.
@@ -575,6 +575,24 @@ int rcot_jpeg_roundtrip(const unsigned char* src, unsigned char* dst, int H, int
  *  RCOT_EUNSUPPORTED (the same): K > 63; an image of 2^31 bytes or more. */
 int rcot_blur_u8(const unsigned char* src, unsigned char* dst, int H, int W, const int* psf, int K, int border, int step, int phase,
                  void* stream);
+
+/* ---- whole-image noise (csrc/noise.hip, where the rule is defined; rcot_amd/chain.py, the noise_<model> stages of a degradation chain) -
+ * src uint8 [H][W][3] (HWC, device) -> dst uint8 [H][W][3]; dst may be src itself, else the two must not overlap.  For byte c of pixel
+ * (y, x) with the value v:
+ *     out = (uint8) clip(v + s z, 0, 255)      product and sum rounded separately in fp32, clip, then truncation (numpy's astype(uint8):
+ *                                              the rule of the denoise_* patches of rcot_patch_prep)
+ *     z   = the library's counter-based standard normal deviate (splitmix64 finaliser of seed + 0x9e3779b97f4a7c15 (idx + 1), Box-Muller
+ *           on two 24-bit uniforms) at the counter idx
+ *   model 0 "g"     s = p0                      idx = (y W + x) 3 + c    white Gaussian noise of sigma p0, channels independent
+ *   model 1 "gray"  s = p0                      idx = y W + x            one deviate shared by R, G and B of a pixel
+ *   model 2 "pg"    s = sqrtf(p0 v + p1 p1)     idx = (y W + x) 3 + c    heteroscedastic (Poisson-Gaussian) noise: variance p0 v + p1^2
+ *   p1 is not read by models 0 and 1.  p0 == 0 (and p1 == 0 for model 2) copies src to dst byte for byte.
+ *   One launch, no workspace, no atomics, 64-bit indices (an image of 2^31 bytes or more is legal), any alignment (16-byte stores where
+ *   src and dst are 16-byte aligned); the result depends on (src, model, p0, p1, seed) alone: bitwise reproducible.
+ *  RCOT_EINVAL (nothing is launched, dst is untouched): a null pointer; H or W < 1; model outside {0, 1, 2}; p0 or p1 negative or not
+ *  finite; p0 > 255 for models 0 and 1. */
+int rcot_noise_u8(const unsigned char* src, unsigned char* dst, int H, int W, int model, float p0, float p1, unsigned long long seed,
+                  void* stream);
 
 #ifdef __cplusplus
 }

@@ -144,6 +144,21 @@ __device__ __forceinline__ void gelu_and_grad(float a, float& g, float& dg) {
     dg = fmaf(a * 0.39894228040143267794f, e, cdf);
 }
 
+__device__ __forceinline__ uint64_t mix64(uint64_t z) {          // splitmix64 finaliser
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+
+// standard normal from a counter (Box-Muller on two 24-bit uniforms): the one noise source of the library — the patch noise of the
+// denoise_* tasks (dataprep.hip) and the whole-image noise of a degradation chain (noise.hip)
+__device__ __forceinline__ float counter_randn(uint64_t seed, uint64_t idx) {
+    const uint64_t h = mix64(seed + 0x9e3779b97f4a7c15ull * (idx + 1));
+    const float u1 = ((float)((h >> 40) & 0xffffff) + 1.0f) * (1.0f / 16777217.0f);     // (0, 1)
+    const float u2 = (float)((h >> 8) & 0xffffff) * (1.0f / 16777216.0f);
+    return sqrtf(-2.0f * __logf(u1)) * __cosf(6.283185307179586f * u2);
+}
+
 // The 8 dihedral maps of numpy's rot90 / flipud composition (the reference's data_augmentation, util/image_utils.py:133-163) on a
 // Th x Tw rectangle: source pixel (sy, sx) of the rectangle for pixel (i, j) of the mapped one.  Modes 0, 1, 4, 5 keep the shape
 // (i < Th, j < Tw); modes 2, 3, 6, 7 give Tw x Th (i < Tw, j < Th).

@@ -15,20 +15,6 @@
 
 namespace {
 
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {          // splitmix64 finaliser
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
-
-// standard normal from a counter (Box-Muller on two 24-bit uniforms)
-__device__ __forceinline__ float counter_randn(uint64_t seed, uint64_t idx) {
-    const uint64_t h = mix64(seed + 0x9e3779b97f4a7c15ull * (idx + 1));
-    const float u1 = ((float)((h >> 40) & 0xffffff) + 1.0f) * (1.0f / 16777217.0f);     // (0, 1)
-    const float u2 = (float)((h >> 8) & 0xffffff) * (1.0f / 16777216.0f);
-    return sqrtf(-2.0f * __logf(u1)) * __cosf(6.283185307179586f * u2);
-}
-
 // One pixel p = i P + j of the mapped patch, all three channels: what both kernels below do per pixel (ONE copy, so row b of the batch
 // kernel runs the instruction sequence of the per-sample kernel and gives its bits, noise included).
 __device__ __forceinline__ void prep_pixel(const unsigned char* __restrict__ deg, const unsigned char* __restrict__ clean, int W, int y0,
@@ -46,7 +32,7 @@ __device__ __forceinline__ void prep_pixel(const unsigned char* __restrict__ deg
             dv = (float)deg[src + c];
         } else {
             // the reference adds noise AFTER the augmentation, element by element of the HWC patch
-            const float v = cv + sigma * counter_randn(seed, ((uint64_t)p) * 3 + c);
+            const float v = cv + sigma * rcot::counter_randn(seed, ((uint64_t)p) * 3 + c);
             dv = floorf(fminf(fmaxf(v, 0.f), 255.f));                        // clip, then astype(uint8) truncation
         }
         clean_out[(long)c * n + p] = cv / 255.0f;            // ToTensor divides (bit-equal to the reference's values)

@@ -6,14 +6,15 @@ image to ONE device kernel (``rcot_patch_prep``) that crops, applies the dihedra
 the denoise_* tasks and converts to CHW float (rcot_amd/csrc/dataprep.hip).  The sr_x2 / sr_x3 / sr_x4 tasks (``--sr_dir``) degrade
 the whole HR image on the device first (rcot_amd/resize.py) and hand both images to the same kernel; the jpeg_q<Q> tasks (``--jpeg_dir``)
 do the same with a baseline JPEG round trip (rcot_amd/jpeg.py), the blur_<spec> tasks (``--blur_dir``) and sr_bd_x3 with a PSF blur
-(rcot_amd/blur.py).  The reference does those steps with PIL/numpy on the host at ``num_workers=0`` (trainer.py:32,134).
+(rcot_amd/blur.py), the chain_<stage>+... tasks (``--chain_dir``) with a chain of those stages and whole-image noise (rcot_amd/chain.py).
+The reference does those steps with PIL/numpy on the host at ``num_workers=0`` (trainer.py:32,134).
 
 ``FolderLoader(..., cache=DeviceImageCache(...))`` (the trainer's ``--data_cache device``, rcot_amd/imagecache.py) keeps every decoded
 image — and the degraded twin of an HR image — on the device after its first use and cuts a whole batch from the resident images in ONE
 launch (``rcot_patch_prep_batch``); the batches are the uncached loader's, bit for bit.
 
 Randomness: the reference leaves python's ``random`` and numpy unseeded; here every draw (epoch
-shuffle, crop origin, augmentation mode 1..7, noise seed, then the angle of a blur_m<L> sample) comes from one
+shuffle, crop origin, augmentation mode 1..7, noise seed, then the angle of a blur_m<L> sample or the draws of a chain) comes from one
 ``random.Random(seed, epoch)`` stream indexed by the GLOBAL sample position, so a run is reproducible and the union of the ranks'
 shards does not depend on the world size.
 """
@@ -103,6 +104,25 @@ def jpeg_dir_or_exit(args, de_type: str) -> str:
     return root
 
 
+def chain_tasks(de_type: Sequence[str]) -> List[tuple]:
+    """the (name, stage records) of every chain_<stage>+... task of a --de_type list, in its order; SystemExit, naming the stage, for a
+    malformed chain"""
+    from .chain import parse_de_type
+    out = []
+    for t in de_type:
+        spec = parse_de_type(t)
+        if spec is not None:
+            out.append((t, spec))
+    return out
+
+
+def chain_dir_or_exit(args, de_type: str) -> str:
+    root = getattr(args, "chain_dir", None)
+    if root is None:
+        raise SystemExit(f"--de_type {de_type} needs --chain_dir DIR, a flat folder of clean images")
+    return root
+
+
 def crop_to_multiple(img: np.ndarray, base: int = 16) -> np.ndarray:
     """util/image_utils.py:59-64 crop_img: centre-crop H and W to multiples of ``base``."""
     h, w = img.shape[0], img.shape[1]
@@ -171,6 +191,13 @@ def build_sample_ids(args) -> List[dict]:
         root = sr_dir_or_exit(args, SR_BD)
         names = sorted(n for n in os.listdir(root) if os.path.isfile(os.path.join(root, n)))
         ids += [{"file": os.path.join(root, n), "de": DE_DICT["single"], "gt": None, "sr": 3, "bd": True} for n in names] * 5
+    for t, spec in chain_tasks(de_type):                                    # "sr": the decode (and the cached image) of sr_x<k>
+        from .chain import size_multiple
+        root = chain_dir_or_exit(args, t)
+        how = (spec, blur_border(args), jpeg_subsampling(args))
+        names = sorted(n for n in os.listdir(root) if os.path.isfile(os.path.join(root, n)))
+        extra = {"sr": size_multiple(spec)} if size_multiple(spec) > 1 else {}
+        ids += [{"file": os.path.join(root, n), "de": DE_DICT["single"], "gt": None, "chain": how, **extra} for n in names] * 5
     return ids
 
 
@@ -245,7 +272,10 @@ class FolderLoader:
         nseed = rng.getrandbits(63)
         dev = self.be.device
         a = torch.from_numpy(img).to(dev, non_blocking=True)
-        if sid.get("bd"):     # super-resolution, BD protocol: blurred, sampled and enlarged again as a whole
+        if sid.get("chain"):  # a degradation chain: every stage sees the WHOLE image; its own draws follow the three common ones
+            assert getattr(self.be, "_plan", None) is None
+            self.be.patch_prep(a, self._chained(rng, sid, a, nseed), y0, x0, P, mode, 0.0, nseed, deg_out, clean_out)
+        elif sid.get("bd"):   # super-resolution, BD protocol: blurred, sampled and enlarged again as a whole
             from .blur import bd_degrade_u8
             assert getattr(self.be, "_plan", None) is None
             self.be.patch_prep(a, bd_degrade_u8(a, self.be), y0, x0, P, mode, 0.0, nseed, deg_out, clean_out)
@@ -273,6 +303,13 @@ class FolderLoader:
         spec, border = sid["blur"]
         angle = rng.randint(0, 179) if needs_angle(spec) else None
         return blur_degrade_u8(a, psf_q_of(spec, angle), border, self.be)
+
+    def _chained(self, rng: random.Random, sid: dict, a, nseed: int):
+        """the degraded twin of the device image ``a`` of a chain sample: the chain's draws come from the sample's stream in stage
+        order, AFTER the crop, mode and noise-seed draws (rcot_amd/chain.py); the noise stages run on seeds derived from ``nseed``"""
+        from .chain import chain_degrade_u8, draw
+        spec, border, sub = sid["chain"]
+        return chain_degrade_u8(a, spec, draw(spec, rng, nseed), border, sub, self.be)
 
     def __iter__(self):
         if self.cache is not None:
@@ -393,7 +430,21 @@ class FolderLoader:
                     y0, x0 = rng.randint(0, H - P), rng.randint(0, W - P)   # the draws of _sample, in its order
                     mode = rng.randint(1, 7)
                     nseed = rng.getrandbits(63)
-                    if sid.get("bd"):
+                    if sid.get("chain"):
+                        from .chain import cacheable, canonical
+                        spec, border, sub = sid["chain"]
+                        if cacheable(spec):                                 # no noise, nothing drawn: one twin per image
+                            key = (sid["file"], "chain", canonical(spec), border, sub)
+                            d = cache.lookup(key)
+                            if d is None:
+                                d = local.get(key)
+                            if d is None:
+                                d = local[key] = cache.offer(key, self._chained(rng, sid, a, nseed))
+                                cache.chain_degradations += 1
+                        else:                                               # noise or per-sample values: the chain runs for every sample
+                            d = self._chained(rng, sid, a, nseed)
+                        rows.append((a, d, y0, x0, mode, 0.0, nseed))
+                    elif sid.get("bd"):
                         key = (sid["file"], "bd", 3)
                         d = cache.lookup(key)
                         if d is None:

@@ -12,6 +12,11 @@ Keys
                                 ``rcot_amd.blur.blur_degrade_u8``; a motion PSF that draws its angle per sample has no resident twin
     (path, "bd", 3)             the twin of an ``sr_bd_x3`` sample (HR image: ``(path, "crop16", "mod", 3)``, shared with ``sr_x3``),
                                 made ONCE by ``rcot_amd.blur.bd_degrade_u8``
+    (path, "chain", name, border, S) the twin of a ``chain_<...>`` sample whose chain has no noise stage and draws nothing per sample
+                                (``rcot_amd.chain.cacheable``; name: ``chain.canonical`` of its stages), made ONCE by
+                                ``rcot_amd.chain.chain_degrade_u8``.  Its clean image is ``(path, "crop16")``, or the ``"mod"`` key of
+                                ``sr_x<k>`` when the chain has such a stage.  Any other chain keeps the decoded image only and runs
+                                for every sample: a noise realisation frozen per image would be learned
 
 Budget: ``budget_bytes`` of image bytes.  An image that would take the total over the budget is not stored: the loader uses it as a
 transient tensor for the batch at hand (stream-ordered allocation keeps it alive until the launch has run) and meets it as a miss
@@ -20,7 +25,7 @@ loader's seed fixes, so a run stays reproducible.
 
 Counters: ``images`` and ``bytes`` resident, ``hits`` and ``misses`` over every resolution of a key, ``sr_degradations`` and
 ``jpeg_degradations`` made (the report names the latter once there is one), ``blur_degradations``: whole-image blurs kept, BD included
-(named last, once there is one).
+(named once there is one), ``chain_degradations``: twins of deterministic chains kept (named last, once there is one).
 """
 from __future__ import annotations
 
@@ -34,6 +39,7 @@ class DeviceImageCache:
         self.budget = max(0, int(budget_bytes))
         self._store = {}
         self.bytes = self.hits = self.misses = self.sr_degradations = self.jpeg_degradations = self.blur_degradations = 0
+        self.chain_degradations = 0
 
     @property
     def images(self) -> int:
@@ -67,4 +73,5 @@ class DeviceImageCache:
         return (f"data cache: {self.images} images, {self.bytes / 2 ** 20:.1f} MiB of {self.budget / 2 ** 30:g} GiB, {self.hits} hits, "
                 f"{self.misses} misses, {self.sr_degradations} sr degradations"
                 + (f", {self.jpeg_degradations} jpeg degradations" if self.jpeg_degradations else "")
-                + (f", {self.blur_degradations} blur degradations" if self.blur_degradations else ""))
+                + (f", {self.blur_degradations} blur degradations" if self.blur_degradations else "")
+                + (f", {self.chain_degradations} chain degradations" if self.chain_degradations else ""))

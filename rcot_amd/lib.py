@@ -9,7 +9,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 33     # == RCOT_ABI_VERSION in include/rcot_hip.h (checked by tests/test_abi.py and at load time)
+ABI_VERSION = 34     # == RCOT_ABI_VERSION in include/rcot_hip.h (checked by tests/test_abi.py and at load time)
 PREC_FP32, PREC_BF16X3, PREC_BF16X6, PREC_BF16X1 = 0, 1, 2, 3     # RCOT_PREC_* of include/rcot_hip.h
 LIB_PATH = os.environ.get("RCOT_LIB") or os.path.join(_HERE, "librcot_hip.so")   # RCOT_LIB: A/B builds while tuning
 
@@ -133,6 +133,8 @@ SIGNATURES = {
     "rcot_jpeg_roundtrip": [_f, _f, _i, _i, _i, _i, _f, _sz, _f],
     # per-image PSF blur (csrc/blur.hip)
     "rcot_blur_u8": [_f, _f, _i, _i, _f, _i, _i, _i, _i, _f],                                  # psf: a DEVICE int32 array
+    # whole-image noise (csrc/noise.hip)
+    "rcot_noise_u8": [_f, _f, _i, _i, _i, _fl, _fl, C.c_ulonglong, _f],
 }
 
 _lib = None

@@ -1535,8 +1535,26 @@ class HipBackend:
                                        step, phase, self._st()), "rcot_blur_u8")
         return out
 
+    # ------------------------------------------------------------------ whole-image noise (csrc/noise.hip)
+    NOISE_MODELS = {"g": 0, "gray": 1, "pg": 2}
+
+    def noise_u8(self, img_u8, model: str, p0: float, p1: float, seed: int, out=None):
+        """img_u8 uint8 [h, w, 3] on the device -> uint8 [h, w, 3]: clip(v + s z, 0, 255) truncated, z a counter-based normal deviate of
+        ``seed``; ``model`` "g" (s = p0, a deviate per byte), "gray" (s = p0, one deviate per pixel) or "pg" (s = sqrt(p0 v + p1^2)).
+        ``out`` may be ``img_u8`` itself (rcot_noise_u8: one launch, no workspace)"""
+        self._u8_image(img_u8, "noise_u8")
+        if model not in self.NOISE_MODELS:
+            raise _lib.RcotKernelError(f"noise_u8: invalid argument: model {model!r}, expected one of {tuple(self.NOISE_MODELS)}")
+        h, w, _ = img_u8.shape
+        if out is None:
+            out = torch.empty(h, w, 3, dtype=torch.uint8, device=self.device)
+        self._u8_image(out, "noise_u8", h, w)
+        _lib.check(self.L.rcot_noise_u8(img_u8.data_ptr(), out.data_ptr(), h, w, self.NOISE_MODELS[model], float(p0), float(p1),
+                                        int(seed) & 0xFFFFFFFFFFFFFFFF, self._st()), "rcot_noise_u8")
+        return out
+
     # ------------------------------------------------------------------ standard image-quality figures (csrc/quality.hip)
-    WINDOWS = {"uniform7": 0, "gauss11": 1}
+    WINDOWS ={"uniform7": 0, "gauss11": 1}
     SPACES = {"rgb": 0, "y": 1}
     QUALITY_TILE = (16, 32)                        # TH x TW of csrc/quality.hip: map positions of one workgroup
 

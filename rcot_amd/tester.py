@@ -61,6 +61,15 @@ replicate|mirror|wrap``; ``--degset`` is not read.  ``--savedeg DIR`` writes tha
 together with ``--sr_scale``, ``--jpeg_q`` or ``--noise_sigma``.  ``--sr_degradation bd`` (with ``--sr_scale 3 --sr_from target`` only)
 replaces the bicubic shrink of the SR input by the BD protocol — Gaussian 7 x 7, sigma 1.6, every third pixel — before the same bicubic
 enlargement; the default ``bicubic`` is the path above.  With neither flag everything runs as before.
+
+Superset: ``--chain SPEC`` evaluates a degradation chain (rcot_amd/chain.py's grammar, with or without the ``chain_`` prefix:
+blur_g1.6+noise_g10+jpeg_q40): the network's input is the whole target — cropped at the top left to a multiple of the scale of an
+``sr_x<k>`` stage — after the stages, made on the device under ``--blur_border`` and ``--jpeg_subsampling``; ``--degset`` is not read.
+The noise seed and the drawn values of a file (ranged parameters, motion angles) come from ``random.Random`` seeded by ``--seed`` and the
+file's index in the sorted ``--tarset`` listing (``chain.file_draws``), so a table row is reproducible and ``--savedeg DIR`` writes the
+bytes ``python -m rcot_amd.chain`` writes for the same seed (after the degradation ``--pad none`` still crops both images to a multiple
+of 4, as for every task; the folder tool does not).  It is refused together with ``--sr_scale``, ``--jpeg_q``, ``--blur`` or
+``--noise_sigma``.
 """
 from __future__ import annotations
 
@@ -121,6 +130,10 @@ parser.add_argument("--blur_border", choices=["replicate", "mirror", "wrap"], de
 parser.add_argument("--sr_degradation", choices=["bicubic", "bd"], default="bicubic",
                     help="superset, with --sr_scale 3 --sr_from target: bd = Gaussian 7 x 7 sigma 1.6 and every third pixel instead of the "
                          "bicubic shrink (the BD rows of SR tables); bicubic = the path as before")
+parser.add_argument("--chain", default=None, type=str,
+                    help="superset: a degradation chain: the network's input is the target after these stages made on the device "
+                         "(rcot_amd/chain.py: blur_g1.6+noise_g10+jpeg_q40; --degset is not read; --seed seeds the per-file values); off by "
+                         "default, everything as before")
 parser.add_argument("--savedeg", default=None, type=str, help="superset: also write the 8-bit network input (with --sr_scale: the bicubic "
                                                              "baseline) as PNGs under this folder")
 
@@ -280,15 +293,25 @@ def _main_any_size(opt, net):
     if opt.blur is not None:
         from .blur import blur_degrade_u8, psf_q_of
         blur_q = psf_q_of(opt.blur)
-    # (sr_from target, jpeg_q, blur: --degset is not read)
-    deg_list = tar_list if sr_target or jpeg_q > 0 or blur_q is not None else sorted(glob.glob(opt.degset + "*"))
+    chain = None
+    if opt.chain is not None:
+        from .chain import degrade_file_u8, parse_spec
+        from .jpeg import SUBSAMPLING
+        chain = parse_spec(opt.chain)
+    # (sr_from target, jpeg_q, blur, chain: --degset is not read)
+    deg_list = tar_list if sr_target or jpeg_q > 0 or blur_q is not None or chain is not None else sorted(glob.glob(opt.degset + "*"))
     rng = np.random.default_rng(opt.seed)
     noisy = opt.noise_sigma is not None
     sizes, stats = [], []
-    for deg_name, tar_name in zip(deg_list, tar_list):
+    for index, (deg_name, tar_name) in enumerate(zip(deg_list, tar_list)):
         name = os.path.basename(tar_name)
         print("Processing ", deg_name)
         deg, tar = np.array(Image.open(deg_name).convert("RGB")), np.array(Image.open(tar_name).convert("RGB"))
+        if chain is not None:
+            pair = degrade_file_u8(tar, chain, opt.seed, index, opt.blur_border, SUBSAMPLING[opt.jpeg_subsampling], be)
+            if pair is None:
+                continue
+            tar, deg = pair
         if S > 0:
             pair = _sr_pair(deg, tar, S, sr_target, be, opt.sr_degradation == "bd")
             if pair is None:
@@ -375,6 +398,12 @@ def main(argv=None):
                 raise ValueError(f"PSF spec {opt.blur!r}: an evaluation blurs with one fixed angle, m<L>a<deg>; {GRAMMAR}")
         except ValueError as e:
             raise SystemExit(f"--blur: {e}")
+    if opt.chain is not None:
+        if opt.sr_scale > 0 or opt.jpeg_q > 0 or opt.blur is not None or opt.noise_sigma is not None:
+            raise SystemExit("--chain makes the network's input from the target: it cannot be combined with --sr_scale, --jpeg_q, --blur "
+                             "or --noise_sigma")
+        from .chain import parse_spec
+        parse_spec(opt.chain)                                         # a malformed chain is refused here, naming the stage
     if opt.sr_degradation == "bd" and (opt.sr_scale != 3 or opt.sr_from != "target"):
         raise SystemExit("--sr_degradation bd is the BD protocol of scale 3 made from the target: it needs --sr_scale 3 --sr_from target")
     if not torch.cuda.is_available():
@@ -384,7 +413,7 @@ def main(argv=None):
     for d in (opt.save, opt.savetar, opt.saveres) + ((opt.savedeg,) if opt.savedeg else ()):
         os.makedirs(d, exist_ok=True)
     net, mult = load_network(opt.model)
-    if opt.pad != "none" or opt.metrics == "device" or opt.sr_scale > 0 or opt.jpeg_q > 0 or opt.blur is not None:
+    if opt.pad != "none" or opt.metrics == "device" or opt.sr_scale > 0 or opt.jpeg_q > 0 or opt.blur is not None or opt.chain is not None:
         return _main_any_size(opt, net)
     deg_list, tar_list = sorted(glob.glob(opt.degset + "*")), sorted(glob.glob(opt.tarset + "*"))
     rng = np.random.default_rng(opt.seed)

@@ -62,6 +62,11 @@ parser.add_argument("--blur_dir", type=str, default=None,
                          "per sample; several may be mixed): a flat folder of sharp images; the whole image is blurred on the device")
 parser.add_argument("--blur_border", choices=["replicate", "mirror", "wrap"], default="replicate",
                     help="--de_type blur_<spec>: the border rule of the blur")
+parser.add_argument("--chain_dir", type=str, default=None,
+                    help="--de_type chain_<stage>+<stage>+... (rcot_amd/chain.py: blur_<spec>, sr_x<k>, jpeg_q<Q> | jpeg_q<Qlo>-<Qhi>, "
+                         "noise_g<s> | noise_gray<s> | noise_pg<a>x<b>, 1 .. 6 stages, e.g. chain_blur_g1.6+noise_g5-20+jpeg_q20-40; "
+                         "several may be mixed): a flat folder of clean images; the stages run on the whole image on the device, "
+                         "--blur_border and --jpeg_subsampling apply to the stages that read them")
 parser.add_argument("--seed", type=int, default=None, help="seed (the reference draws an unseeded random one)")
 parser.add_argument("--prec", choices=["fp32", "bf16x6", "bf16x3", "bf16x1"], default=os.environ.get("RCOT_GEMM_PREC", "fp32"),
                     help="arithmetic of the 1x1 MFMA products (include/rcot_hip.h RCOT_PREC_*; one default for HipBackend(), this CLI and "
@@ -77,7 +82,7 @@ parser.add_argument("--val_pad", choices=["none", "reflect", "replicate"], defau
                          "(rcot_amd/wholeimage.py); none = the reference's rule, images that are not multiples of 8 are skipped")
 parser.add_argument("--data_cache", choices=["off", "device"], default="off",
                     help="device: every training image is decoded once and stays on the device as uint8 (a super-resolution image with "
-                         "its degraded twin, made once, the JPEG twin of a jpeg_q<Q> image and the blurred twin of a blur_<spec> image with a fixed PSF); a batch is cut from the resident images in one launch "
+                         "its degraded twin, made once, the JPEG twin of a jpeg_q<Q> image the blurred twin of a blur_<spec> image with a fixed PSF and the twin of a chain without noise or per-sample values); a batch is cut from the resident images in one launch "
                          "(rcot_amd/imagecache.py).  The batches are those of `off`, bit for bit.  Ignored with --synthetic")
 parser.add_argument("--data_cache_gb", type=float, default=16.0,
                     help="--data_cache device: budget of image bytes per rank, in GiB; an image that does not fit is decoded again "
@@ -132,6 +137,20 @@ def check_blur_flags(o) -> None:
         blur_border(o)
     if bd:
         sr_dir_or_exit(o, SR_BD)
+
+
+def check_chain_flags(o) -> None:
+    """the degradation chains chain_<stage>+... read clean images from --chain_dir and degrade them on the device: a malformed chain
+    (the message names the stage), a missing folder and --synthetic are refused up front"""
+    from .data import blur_border, chain_dir_or_exit, chain_tasks, jpeg_subsampling
+    tasks = chain_tasks(o.de_type)
+    if not tasks:
+        return
+    if o.synthetic:
+        raise SystemExit(f"--de_type {tasks[0][0]} degrades whole images from --chain_dir: it cannot be combined with --synthetic")
+    chain_dir_or_exit(o, tasks[0][0])
+    blur_border(o)
+    jpeg_subsampling(o)
 
 
 def check_patch_size(P: int) -> int:
@@ -687,6 +706,7 @@ def main(argv=None):
     check_sr_flags(opt)
     check_jpeg_flags(opt)
     check_blur_flags(opt)
+    check_chain_flags(opt)
     # --backbone mprnet: with a GPU the older transport map runs on the HIP kernels (rcot_amd/mprnet_hip.py) through everything below —
     # data folders, data parallelism, validation, launch plans; without one (or with RCOT_MPRNET_STOCK=1) the stock-ops loop
     hip_mprnet = opt.backbone == "mprnet" and torch.cuda.is_available() and os.environ.get("RCOT_MPRNET_STOCK", "0") != "1"
