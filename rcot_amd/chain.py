@@ -250,16 +250,8 @@ def degrade_file_u8(img: np.ndarray, spec, seed: int, index: int, border: str, s
     """one file of a folder: uint8 [H, W, 3] on the host -> (clean, degraded) uint8 arrays of one size — the image cropped at the top
     left to a multiple of ``size_multiple(spec)``, and its chain under ``file_draws(spec, seed, index)`` — or None, with a message,
     for an image a stage cannot take"""
-    m = size_multiple(spec)
-    img = np.ascontiguousarray(img[:img.shape[0] - img.shape[0] % m, :img.shape[1] - img.shape[1] % m])
-    if img.shape[0] < m or img.shape[1] < m:
-        print(f"  skipped: {img.shape[0]} x {img.shape[1]} is smaller than the scale factor {m}")
-        return None
-    if subsampling == 2 and img.shape[1] <= 4 and any(st[0] == "jpeg" for st in spec):
-        print(f"  skipped: {img.shape[0]} x {img.shape[1]} is not wider than 4 pixels (4:2:0)")
-        return None
-    d = torch.from_numpy(img).to(be.device)
-    return img, chain_degrade_u8(d, spec, file_draws(spec, seed, index), border, subsampling, be).cpu().numpy()
+    from . import degrade                                   # the step of every whole-image task; the tester's too
+    return degrade.degrade_file_u8(img, degrade.BY_FIELD["chain"].fields(spec, border, subsampling), file_draws(spec, seed, index), be)
 
 
 # ------------------------------------------------------------------ the folder CLI

@@ -2,7 +2,8 @@
 ``FolderLoader(..., cache=...)`` (rcot_amd/data.py) cuts a whole batch from resident images in one launch (``patch_prep_batch``)
 instead of decoding, uploading and — for the super-resolution tasks — degrading the files of every sample again.
 
-Keys
+Keys (a file's: ``FolderLoader._file_keys``; a twin's: the ``key`` of its family's entry in rcot_amd/degrade.py, which also names the
+entry point that makes it and the counter it counts under)
     (path, "crop16")            a decoded file after ``crop_to_multiple(..., 16)``
     (path, "crop16", "mod", s)  the HR image of an ``sr_x<s>`` sample after the further top-left crop to a multiple of ``s``
     (path, "sr", s)             its degraded twin, made ONCE by ``rcot_amd.resize.sr_degrade_u8``
@@ -25,7 +26,8 @@ loader's seed fixes, so a run stays reproducible.
 
 Counters: ``images`` and ``bytes`` resident, ``hits`` and ``misses`` over every resolution of a key, ``sr_degradations`` and
 ``jpeg_degradations`` made (the report names the latter once there is one), ``blur_degradations``: whole-image blurs kept, BD included
-(named once there is one), ``chain_degradations``: twins of deterministic chains kept (named last, once there is one).
+(named once there is one), ``chain_degradations``: twins of deterministic chains kept (named last, once there is one).  The loader
+counts a twin where it makes it, through ``count(counter)``.
 """
 from __future__ import annotations
 
@@ -68,6 +70,10 @@ class DeviceImageCache:
             self._store[key] = img
             self.bytes += img.numel()
         return img
+
+    def count(self, counter: str):
+        """one more degraded twin made under ``counter``: "sr", "jpeg", "blur" or "chain" (rcot_amd/degrade.py names it per task)"""
+        setattr(self, counter + "_degradations", getattr(self, counter + "_degradations") + 1)
 
     def report(self) -> str:
         return (f"data cache: {self.images} images, {self.bytes / 2 ** 20:.1f} MiB of {self.budget / 2 ** 30:g} GiB, {self.hits} hits, "

@@ -250,35 +250,42 @@ def _report(psnr, ssim, pmax, smax, pmin, smin, done, ssim_window="box2", color=
                 ssim_window=ssim_window, color=color)
 
 
-def _sr_pair(deg: np.ndarray, tar: np.ndarray, S: int, from_target: bool, be, bd: bool = False):
-    """``--sr_scale S``: (network input, target) as uint8 [H, W, 3] arrays of one size, or None (with a message) for a pair that is
-    skipped.  from_target: the target is cropped at the top left to a multiple of S and degraded (down, 8 bits, up, 8 bits).  Else
-    ``deg`` is the h x w LR image: it is enlarged to hS x wS, and the target is cropped to that at the top left — it may be larger by
-    less than S in either direction (what the crop to a multiple of S removed when the LR image was made).  ``bd`` (from_target, S = 3):
-    the degradation is rcot_amd.blur.bd_degrade_u8."""
-    from .resize import sr_degrade_u8, sr_upscale_u8
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(be.device)
-    if from_target:
-        H, W = tar.shape[0] - tar.shape[0] % S, tar.shape[1] - tar.shape[1] % S
-        if H < S or W < S:
-            print(f"  skipped: target {tar.shape[0]} x {tar.shape[1]} is smaller than the scale factor {S}")
-            return None
-        tar = np.ascontiguousarray(tar[:H, :W])
-        if bd:
-            from .blur import bd_degrade_u8
-            return bd_degrade_u8(up(tar), be).cpu().numpy(), tar
-        return sr_degrade_u8(up(tar), S, be).cpu().numpy(), tar
+def _target_task(opt):
+    """the whole-image task (a sample's fields, rcot_amd/degrade.py) that makes the network's input from the target — ``--chain``,
+    ``--sr_scale S --sr_from target`` (bicubic, or ``--sr_degradation bd``), ``--jpeg_q`` or ``--blur``, which main() lets through one
+    at a time — or None"""
+    from .degrade import BY_FIELD, blur_border, jpeg_subsampling
+    if opt.chain is not None:
+        from .chain import parse_spec
+        return BY_FIELD["chain"].fields(parse_spec(opt.chain), blur_border(opt), jpeg_subsampling(opt))
+    if opt.sr_scale > 0 and opt.sr_from == "target":
+        return BY_FIELD["bd"].fields(True) if opt.sr_degradation == "bd" else BY_FIELD["sr"].fields(opt.sr_scale)
+    if opt.jpeg_q > 0:
+        return BY_FIELD["jpeg"].fields(opt.jpeg_q, jpeg_subsampling(opt))
+    if opt.blur is not None:
+        return BY_FIELD["blur"].fields(opt.blur, blur_border(opt))
+    return None
+
+
+def _sr_from_lr(deg: np.ndarray, tar: np.ndarray, S: int, be):
+    """``--sr_scale S --sr_from lr``: (network input, target) as uint8 [H, W, 3] arrays of one size, or None (with a message) for a
+    pair that is skipped.  ``deg`` is the h x w LR image: it is enlarged to hS x wS, and the target is cropped to that at the top left
+    — it may be larger by less than S in either direction (what the crop to a multiple of S removed when the LR image was made)"""
+    from .resize import sr_upscale_u8
     H, W = deg.shape[0] * S, deg.shape[1] * S
     if tar.shape[0] < H or tar.shape[1] < W or tar.shape[0] - H >= S or tar.shape[1] - W >= S:
         print(f"  skipped: LR {deg.shape[0]} x {deg.shape[1]} times {S} is {H} x {W}, the target is {tar.shape[0]} x {tar.shape[1]}")
         return None
-    return sr_upscale_u8(up(deg), H, W, be).cpu().numpy(), np.ascontiguousarray(tar[:H, :W])
+    lr = torch.from_numpy(np.ascontiguousarray(deg)).to(be.device)
+    return sr_upscale_u8(lr, H, W, be).cpu().numpy(), np.ascontiguousarray(tar[:H, :W])
 
 
 def _main_any_size(opt, net):
     """``--pad`` other than none and / or ``--metrics device``: ingest (or pad2d for the noisy float input), the network on the padded
     image, and the egress kernel for the crop, the three 8-bit images and the statistics.  The size multiple is the network's own."""
     from PIL import Image
+    from .chain import file_draws
+    from .degrade import degrade_file_u8
     from .wholeimage import image_metrics, pad_geometry, restore_any_size
     be, mult = net.be, net.size_multiple
     padded = opt.pad != "none"
@@ -286,20 +293,8 @@ def _main_any_size(opt, net):
     standard = _standard(opt)                                         # rcot_image_quality instead of the egress kernel's own sums
     proto = (opt.ssim_window, opt.color)
     tar_list = sorted(glob.glob(opt.tarset + "*"))
-    S = opt.sr_scale
-    sr_target = S > 0 and opt.sr_from == "target"
-    jpeg_q = opt.jpeg_q
-    blur_q = None
-    if opt.blur is not None:
-        from .blur import blur_degrade_u8, psf_q_of
-        blur_q = psf_q_of(opt.blur)
-    chain = None
-    if opt.chain is not None:
-        from .chain import degrade_file_u8, parse_spec
-        from .jpeg import SUBSAMPLING
-        chain = parse_spec(opt.chain)
-    # (sr_from target, jpeg_q, blur, chain: --degset is not read)
-    deg_list = tar_list if sr_target or jpeg_q > 0 or blur_q is not None or chain is not None else sorted(glob.glob(opt.degset + "*"))
+    task = _target_task(opt)                                          # the input is made from the target: --degset is not read
+    deg_list = tar_list if task is not None else sorted(glob.glob(opt.degset + "*"))
     rng = np.random.default_rng(opt.seed)
     noisy = opt.noise_sigma is not None
     sizes, stats = [], []
@@ -307,25 +302,19 @@ def _main_any_size(opt, net):
         name = os.path.basename(tar_name)
         print("Processing ", deg_name)
         deg, tar = np.array(Image.open(deg_name).convert("RGB")), np.array(Image.open(tar_name).convert("RGB"))
-        if chain is not None:
-            pair = degrade_file_u8(tar, chain, opt.seed, index, opt.blur_border, SUBSAMPLING[opt.jpeg_subsampling], be)
+        if task is not None:                                          # (a chain's per-file values: the rule of its folder tool)
+            drawn = file_draws(task["chain"][0], opt.seed, index) if "chain" in task else None
+            # the wording of a skip is each flag's own: --chain speaks as its folder tool does (the size after the crop, no noun), the
+            # other three name the "target" at the size it was read
+            pair = degrade_file_u8(tar, task, drawn, be, "" if "chain" in task else "target")
             if pair is None:
                 continue
             tar, deg = pair
-        if S > 0:
-            pair = _sr_pair(deg, tar, S, sr_target, be, opt.sr_degradation == "bd")
+        elif opt.sr_scale > 0:
+            pair = _sr_from_lr(deg, tar, opt.sr_scale, be)
             if pair is None:
                 continue
             deg, tar = pair
-        if jpeg_q > 0:
-            from .jpeg import SUBSAMPLING, jpeg_degrade_u8
-            sub = SUBSAMPLING[opt.jpeg_subsampling]
-            if sub == 2 and tar.shape[1] <= 4:
-                print(f"  skipped: target {tar.shape[0]} x {tar.shape[1]} is not wider than 4 pixels (4:2:0)")
-                continue
-            deg = jpeg_degrade_u8(torch.from_numpy(np.ascontiguousarray(tar)).to(be.device), jpeg_q, sub, be).cpu().numpy()
-        if blur_q is not None:
-            deg = blur_degrade_u8(torch.from_numpy(np.ascontiguousarray(tar)).to(be.device), blur_q, opt.blur_border, be).cpu().numpy()
         if deg.shape != tar.shape:
             print(f"  skipped: degraded {deg.shape[0]} x {deg.shape[1]} and target {tar.shape[0]} x {tar.shape[1]} differ")
             continue

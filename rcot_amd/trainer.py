@@ -96,61 +96,20 @@ DE_IDS = {"denoise_15": 0, "denoise_25": 1, "denoise_50": 2, "derain": 3, "dehaz
           "lowlight": 6, "single": 7}   # util/dataset_utils.py:40
 
 
-def check_sr_flags(o) -> None:
-    """the super-resolution tasks read HR images from --sr_dir and degrade them on the device: refused up front without the folder
-    or with --synthetic (seeded patches have no image to resize)"""
-    from .data import SR_SCALE, sr_dir_or_exit
-    sr = [t for t in o.de_type if t in SR_SCALE]
-    if not sr:
-        return
-    if o.synthetic:
-        raise SystemExit(f"--de_type {sr[0]} degrades whole images from --sr_dir: it cannot be combined with --synthetic")
-    sr_dir_or_exit(o, sr[0])
-
-
-def check_jpeg_flags(o) -> None:
-    """the compression-artifact tasks jpeg_q<Q> read clean images from --jpeg_dir and degrade them on the device: a malformed name, a
-    quality outside 1 .. 100, a missing folder and --synthetic are refused up front"""
-    from .data import jpeg_dir_or_exit, jpeg_subsampling, jpeg_tasks
-    tasks = jpeg_tasks(o.de_type)
-    if not tasks:
-        return
-    if o.synthetic:
-        raise SystemExit(f"--de_type {tasks[0][0]} degrades whole images from --jpeg_dir: it cannot be combined with --synthetic")
-    jpeg_dir_or_exit(o, tasks[0][0])
-    jpeg_subsampling(o)
-
-
-def check_blur_flags(o) -> None:
-    """the deblurring tasks blur_<spec> read sharp images from --blur_dir, sr_bd_x3 HR images from --sr_dir, and both blur them on the
-    device: a malformed name, a missing folder and --synthetic are refused up front"""
-    from .data import SR_BD, blur_border, blur_dir_or_exit, blur_tasks, sr_dir_or_exit
-    tasks = blur_tasks(o.de_type)
-    bd = SR_BD in o.de_type
-    if not tasks and not bd:
-        return
-    if o.synthetic:
-        name, flag = (tasks[0][0], "--blur_dir") if tasks else (SR_BD, "--sr_dir")
-        raise SystemExit(f"--de_type {name} degrades whole images from {flag}: it cannot be combined with --synthetic")
-    if tasks:
-        blur_dir_or_exit(o, tasks[0][0])
-        blur_border(o)
-    if bd:
-        sr_dir_or_exit(o, SR_BD)
-
-
-def check_chain_flags(o) -> None:
-    """the degradation chains chain_<stage>+... read clean images from --chain_dir and degrade them on the device: a malformed chain
-    (the message names the stage), a missing folder and --synthetic are refused up front"""
-    from .data import blur_border, chain_dir_or_exit, chain_tasks, jpeg_subsampling
-    tasks = chain_tasks(o.de_type)
-    if not tasks:
-        return
-    if o.synthetic:
-        raise SystemExit(f"--de_type {tasks[0][0]} degrades whole images from --chain_dir: it cannot be combined with --synthetic")
-    chain_dir_or_exit(o, tasks[0][0])
-    blur_border(o)
-    jpeg_subsampling(o)
+def check_degradation_flags(o) -> None:
+    """the whole-image tasks (rcot_amd/degrade.py: sr_x<k>, jpeg_q<Q>, blur_<spec>, sr_bd_x3, chain_<...>) read clean images from their
+    folder and degrade them on the device: a malformed name (a chain's message names the stage), --synthetic (seeded patches have no
+    image to degrade), a missing folder and a bad option flag are refused up front, family by family"""
+    from . import degrade
+    for task in degrade.TASKS:
+        tasks = degrade.named(task, o.de_type)
+        if not tasks:
+            continue
+        if o.synthetic:
+            raise SystemExit(f"--de_type {tasks[0][0]} degrades whole images from --{task.folder}: it cannot be combined with --synthetic")
+        degrade.folder(task, o, tasks[0][0])
+        for read in task.options:
+            read(o)
 
 
 def check_patch_size(P: int) -> int:
@@ -703,10 +662,7 @@ def main(argv=None):
         check_patch_size(opt.patch_size)                   # before any network is built or the GPU is touched
     except ValueError as e:
         raise SystemExit(str(e))
-    check_sr_flags(opt)
-    check_jpeg_flags(opt)
-    check_blur_flags(opt)
-    check_chain_flags(opt)
+    check_degradation_flags(opt)
     # --backbone mprnet: with a GPU the older transport map runs on the HIP kernels (rcot_amd/mprnet_hip.py) through everything below —
     # data folders, data parallelism, validation, launch plans; without one (or with RCOT_MPRNET_STOCK=1) the stock-ops loop
     hip_mprnet = opt.backbone == "mprnet" and torch.cuda.is_available() and os.environ.get("RCOT_MPRNET_STOCK", "0") != "1"

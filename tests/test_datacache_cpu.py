@@ -1,6 +1,7 @@
 """CPU tier: the device-resident training set (rcot_amd/imagecache.py) behind ``FolderLoader(..., cache=...)`` on the miniature tree
 of tests/test_data_cpu.py — the cached loader's batches equal the uncached loader's bit for bit over two epochs and across ranks,
-every file is decoded once, the budget rule, and the host check of ``patch_prep_batch``'s rows.  Kernel layer: a subclass of the
+every file is decoded once, the budget rule, the host check of ``patch_prep_batch``'s rows, and the loader's call trace over every
+task family against the trace recorded before the whole-image tasks moved into one table (tests/loader_trace.py).  Kernel layer: a subclass of the
 numpy test double whose ``patch_prep_batch`` loops over its ``patch_prep``."""
 import os
 from argparse import Namespace
@@ -173,6 +174,28 @@ def test_row_check_refuses_before_any_launch():
         check_patch_rows([], P, d, c)
     with pytest.raises(ValueError):
         check_patch_rows([ok], 0, d, c)
+
+
+def test_call_trace_of_every_family_is_the_recorded_one(tmp_path):
+    """tests/golden/loader_trace.json (scripts/make_loader_trace_fixture.py; recorded from the commit the file names, the parent of the
+    change that put the whole-image tasks into one table): every draw, entry-point call, patch_prep row, batch, cache insertion and
+    counter of all task families at once — uncached, cached at two budgets, world 1 and both ranks of world 2, two epochs — held
+    batch by batch through a SHA-256 that runs over every entry of the log (tests/loader_trace.py::digest)"""
+    import json
+    import loader_trace as LT
+    from conftest import GOLD
+    want = json.load(open(os.path.join(GOLD, "loader_trace.json")))
+    log = json.loads(json.dumps(LT.record(tmp_path)))                       # tuples as the lists JSON makes of them
+    got = LT.digest(log)
+    assert [r["run"] for r in got] == [r["run"] for r in want["runs"]] and len(got) == 9
+    for g, w in zip(got, want["runs"]):
+        first = next((k for k, (x, y) in enumerate(zip(g["batches"], w["batches"])) if x != y), None)
+        assert first is None and len(g["batches"]) == len(w["batches"]), (g["run"], "first batch that differs", first)
+        assert g["cache"] == w["cache"], g["run"]
+    assert len(log) == want["entries"] == 2803
+    kinds = {e[0] for e in log}
+    assert kinds == {"ids", "run", "batch", "cache", "patch_prep", "patch_prep_batch", "sr_degrade_u8", "jpeg_degrade_u8", "blur_degrade_u8",
+                     "bd_degrade_u8", "chain_degrade_u8"}
 
 
 def test_trainer_flags():

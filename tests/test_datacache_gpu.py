@@ -165,6 +165,37 @@ def test_cached_loader_equals_uncached_on_the_device(hip, tmp_path, monkeypatch)
     assert not torch.equal(got[0][1], got[187][1])
 
 
+def test_every_task_family_at_once_cached_equals_uncached(hip, tmp_path):
+    """the --de_type list of tests/loader_trace.py — denoise, a paired task, sr_x2, sr_x3, sr_bd_x3, jpeg_q10, blur_g1.6, blur_m15, a
+    cacheable chain with an SR stage and a drawn chain — on its three images of 48 x 64, 50 x 70 and 66 x 81 (the crops to 16 and to
+    3 both act: 50 x 70 -> 48 x 64 -> 48 x 63); P = 32, batch 4, two epochs of 150 samples"""
+    import loader_trace as LT
+    from rcot_amd import chain as C
+    from rcot_amd import data as D
+    from rcot_amd.imagecache import DeviceImageCache
+    args = LT.tree(str(tmp_path))
+    cache = DeviceImageCache(hip, 1 << 30)
+    cached = D.FolderLoader(args, 4, seed=LT.SEED, backend=hip, threads=4, cache=cache)
+    plain = D.FolderLoader(args, 4, seed=LT.SEED, backend=hip, threads=4)
+    got, want = [b for _ in range(2) for b in cached], [b for _ in range(2) for b in plain]
+    assert len(got) == len(want) == 2 * 38
+    for k, (([n1, l1], d1, c1), ([n2, l2], d2, c2)) in enumerate(zip(got, want)):
+        assert n1 == n2 and torch.equal(l1, l2), k
+        assert torch.equal(d1, d2) and torch.equal(c1, c2), k
+    assert not torch.equal(got[0][1], got[38][1]) and not torch.equal(got[0][2], got[38][2])      # the second epoch is another epoch
+    files = len(LT.SIZES)
+    assert cache.sr_degradations == files * 2                                 # sr_x2, sr_x3
+    assert cache.jpeg_degradations == files * 1                               # jpeg_q10
+    assert cache.blur_degradations == files * 2                               # blur_g1.6, sr_bd_x3 (blur_m15 draws its angle)
+    assert cache.chain_degradations == files * 1                              # chain_sr_x3+blur_g1.6 (the other chain draws)
+    clean = [f"{tmp_path}/clean/{n}.png" for n in LT.SIZES]
+    twins = {k for k in cache.keys() if k[1] != "crop16"}
+    kept = C.canonical(C.parse_de_type("chain_sr_x3+blur_g1.6"))
+    assert twins == {key for f in clean for key in ((f, "sr", 2), (f, "sr", 3), (f, "bd", 3), (f, "jpeg", 10, 0), (f, "blur", "g1.6", "mirror"),
+                                                    (f, "chain", kept, "mirror", 0))}      # no twin of blur_m15 or of the drawn chain
+    assert cache.images == len(twins) + 3 * files + 2 * files == cache.misses  # + crop16, mod 2, mod 3; + the paired task's two folders
+
+
 def test_trainer_cli_with_the_device_cache(tmp_path):
     """--data_cache device on synth_folders.dataset_tree: 3 files, 15 samples, two epochs of 5 iterations at P = 32"""
     root = str(tmp_path)
