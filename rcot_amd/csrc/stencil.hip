@@ -20,10 +20,14 @@ struct Row6 { float v[6]; };
 struct Patch { Row6 r[6]; };       // rows y0-1..y0+4 of a 4x4 output block
 
 __device__ __forceinline__ float from_lane_below(float v) {      // lane i <- lane i-1   (v_mov_b32_dpp wave_shr:1)
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, false));
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, true));
 }
 __device__ __forceinline__ float from_lane_above(float v) {      // lane i <- lane i+1   (wave_shl:1)
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, false));
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, true));
+}
+
+__device__ __forceinline__ float keep_bits(float v, int mask) {   // v (mask = -1) or +0.0 (mask = 0), bit for bit
+    return __builtin_bit_cast(float, __builtin_bit_cast(int, v) & mask);
 }
 
 // row y of the plane (zeros outside it) with scalar-load halo pixels
@@ -45,7 +49,9 @@ __device__ __forceinline__ void load_row6(const float* __restrict__ plane, int H
 // sits under a condition that differs between the lanes of a row; the kernels REQUEST their rows beforehand (unconditional 16-byte
 // loads from clamped row indices): a load inside `if (row exists)` followed by the lane shift costs one full memory round trip per row.
 __device__ __forceinline__ void land_row6(const float4& q, bool ok, bool has_l, bool has_r, Row6& r) {
-    const float4 c = ok ? q : make_float4(0.f, 0.f, 0.f, 0.f);
+    // zeros by a bit mask, one v_and per value: as `ok ? q : 0` the compiler builds a branch around four copies (eight v_mov per row)
+    const int m = ok ? -1 : 0;
+    const float4 c = make_float4(keep_bits(q.x, m), keep_bits(q.y, m), keep_bits(q.z, m), keep_bits(q.w, m));
     const float l = from_lane_below(c.w), rr = from_lane_above(c.x);
     r.v[0] = has_l ? l : 0.f;
     r.v[1] = c.x; r.v[2] = c.y; r.v[3] = c.z; r.v[4] = c.w;
@@ -78,13 +84,16 @@ __device__ __forceinline__ void patch_land(const PatchRows& q, int H, int W, int
 }
 
 // one output quad from three input rows
+// (ROT: with the 180-degree rotated filter, read in place as w[8 - i])
+template <bool ROT = false>
 __device__ __forceinline__ void stencil_row(const Row6& a, const Row6& b, const Row6& c, const float (&w)[9], float (&o)[4]) {
+    constexpr int o0 = ROT ? 8 : 0, st = ROT ? -1 : 1;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {                                  // explicit FMAs: the file is built with -ffp-contract=off
-        float t = w[0] * a.v[j];
-        t = fmaf(w[1], a.v[j + 1], t); t = fmaf(w[2], a.v[j + 2], t);
-        t = fmaf(w[3], b.v[j], t); t = fmaf(w[4], b.v[j + 1], t); t = fmaf(w[5], b.v[j + 2], t);
-        t = fmaf(w[6], c.v[j], t); t = fmaf(w[7], c.v[j + 1], t); t = fmaf(w[8], c.v[j + 2], t);
+        float t = w[o0] * a.v[j];
+        t = fmaf(w[o0 + st], a.v[j + 1], t); t = fmaf(w[o0 + 2 * st], a.v[j + 2], t);
+        t = fmaf(w[o0 + 3 * st], b.v[j], t); t = fmaf(w[o0 + 4 * st], b.v[j + 1], t); t = fmaf(w[o0 + 5 * st], b.v[j + 2], t);
+        t = fmaf(w[o0 + 6 * st], c.v[j], t); t = fmaf(w[o0 + 7 * st], c.v[j + 1], t); t = fmaf(w[o0 + 8 * st], c.v[j + 2], t);
         o[j] = t;
     }
 }
@@ -98,8 +107,8 @@ __device__ __forceinline__ void stencil16(const Patch& p, const float* __restric
 }
 
 // the two gate derivatives of one quad from the depthwise outputs d1, d2 and dg:  av = dg * d2 * gelu'(d1),  cv = dg * gelu(d1)
-__device__ __forceinline__ void gate_grad_row(const float4& gq, const float (&d1)[4], const float (&d2)[4], float (&av)[4],
-                                              float (&cv)[4]) {
+// (av, cv: four floats each, wherever the caller keeps them)
+__device__ __forceinline__ void gate_grad_row(const float4& gq, const float (&d1)[4], const float (&d2)[4], float* av, float* cv) {
     const float gv[4] = {gq.x, gq.y, gq.z, gq.w};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -368,11 +377,9 @@ __global__ __launch_bounds__(256) void gdfn_bwd_kernel(const float* __restrict__
     float* o1 = dp + (bi * 2 * hid + j) * hw;
     float* o2 = o1 + (long)hid * hw;
     const float* gp = dg + b.plane * hw;
-    float w1[9], w2[9], f1[9], f2[9];
+    float w1[9], w2[9];
 #pragma unroll
     for (int i = 0; i < 9; ++i) { w1[i] = w[j * 9 + i]; w2[i] = w[(j + hid) * 9 + i]; }
-#pragma unroll
-    for (int i = 0; i < 9; ++i) { f1[i] = w1[8 - i]; f2[i] = w2[8 - i]; }      // 180-degree rotated filters
     const bool has_l = b.x0 > 0, has_r = b.x0 + 4 < W;
     float s[18];
 #pragma unroll
@@ -380,22 +387,25 @@ __global__ __launch_bounds__(256) void gdfn_bwd_kernel(const float* __restrict__
     Row6 a1[3], a2[3];            // p rows   y0-2+q   in slot q % 3
     Row6 e1[3], e2[3];            // dd rows  y0-1+i   in slot i % 3   (v[0], v[5] = halo columns)
     // Software pipeline: the three 16-byte loads an iteration needs (row r+1 of both p planes, row r of dg) are REQUESTED one
-    // iteration ahead, unconditionally, from clamped row indices (out-of-range rows and dead tail threads are zeroed by selects
+    // iteration ahead, unconditionally, from clamped row indices (out-of-range rows and dead tail threads are zeroed by masks
     // when the data lands).  With the loads inside `if (row exists)` blocks each one was followed by s_waitcnt vmcnt(0) — three
     // serialised memory round trips per row, 54 per strip (ISA of round 3, scripts/README.md "stencil ISA").
+    // One iteration and no more: two rows ahead fit the registers of three waves per SIMD only with the filters held in SGPRs, and
+    // then measured the same at 128x128 and 3-6 % slower at 64x64 and 32x32; every row of a 4-row strip ahead costs the third
+    // wave and 5-9 % (profiles/stencil_issue_diet.txt).
     float4 n1, n2, ng;
-    auto request = [&](int yp, int yg) {
-        const int ypc = min(max(yp, 0), H - 1), ygc = min(max(yg, 0), H - 1);
+    auto request = [&](int yp, bool with_g) {                   // row yp of both p planes, row yp - 1 of dg
+        const int ypc = min(max(yp, 0), H - 1);
         n1 = *reinterpret_cast<const float4*>(p1 + (long)ypc * W + b.x0);
         n2 = *reinterpret_cast<const float4*>(p2 + (long)ypc * W + b.x0);
-        ng = *reinterpret_cast<const float4*>(gp + (long)ygc * W + b.x0);
+        if (with_g) ng = *reinterpret_cast<const float4*>(gp + (long)min(max(yp - 1, 0), H - 1) * W + b.x0);
     };
     auto land = [&](const float4& q, int y, Row6& r) { land_row6(q, b.live && y >= 0 && y < H, has_l, has_r, r); };
-    request(b.y0 - 2, 0);
+    request(b.y0 - 2, false);
     land(n1, b.y0 - 2, a1[0]); land(n2, b.y0 - 2, a2[0]);
-    request(b.y0 - 1, 0);
+    request(b.y0 - 1, false);
     land(n1, b.y0 - 1, a1[1]); land(n2, b.y0 - 1, a2[1]);
-    request(b.y0, b.y0 - 1);
+    request(b.y0, true);
 #pragma unroll
     for (int i = 0; i < RS + 2; ++i) {
         const int r = b.y0 - 1 + i;                             // dd row formed in this iteration
@@ -404,35 +414,35 @@ __global__ __launch_bounds__(256) void gdfn_bwd_kernel(const float* __restrict__
         land(n1, r + 1, dn1);
         land(n2, r + 1, dn2);
         const float4 gq = ng;
-        if (i < RS + 1) request(r + 2, r + 1);                  // next iteration's rows fly under this iteration's arithmetic
-        float av[4] = {0.f, 0.f, 0.f, 0.f}, cv[4] = {0.f, 0.f, 0.f, 0.f};
+        if (i < RS + 1) request(r + 2, true);                   // next iteration's rows fly under this iteration's arithmetic
+        Row6& ec1 = e1[i % 3];                                  // the dd rows are formed in place: v[1..4]
+        Row6& ec2 = e2[i % 3];
         if (b.live && r >= 0 && r < H) {
             float d1[4], d2[4];
             stencil_row(up1, mid1, dn1, w1, d1);
             stencil_row(up2, mid2, dn2, w2, d2);
-            gate_grad_row(gq, d1, d2, av, cv);
+            gate_grad_row(gq, d1, d2, ec1.v + 1, ec2.v + 1);
             if (i >= 1 && i <= RS) {                            // rows of this strip: weight gradient (halo rows belong to others)
-                wgrad_row(av, up1, mid1, dn1, s);
-                wgrad_row(cv, up2, mid2, dn2, s + 9);
+                wgrad_row(ec1.v + 1, up1, mid1, dn1, s);
+                wgrad_row(ec2.v + 1, up2, mid2, dn2, s + 9);
             }
+        } else {
+#pragma unroll
+            for (int k = 1; k < 5; ++k) ec1.v[k] = ec2.v[k] = 0.f;
         }
         // the halo columns of the two dd rows from the neighbouring lanes, outside the condition above: the four shifts issued together
         // (through land_row6, two and two, the kernel is 1.8 % longer: 8599 against 8445 instructions at <256, 16>)
-        Row6& ec1 = e1[i % 3];
-        Row6& ec2 = e2[i % 3];
-        const float l1 = from_lane_below(av[3]), r1 = from_lane_above(av[0]);
-        const float l2 = from_lane_below(cv[3]), r2 = from_lane_above(cv[0]);
+        const float l1 = from_lane_below(ec1.v[4]), r1 = from_lane_above(ec1.v[1]);
+        const float l2 = from_lane_below(ec2.v[4]), r2 = from_lane_above(ec2.v[1]);
         ec1.v[0] = has_l ? l1 : 0.f; ec1.v[5] = has_r ? r1 : 0.f;
         ec2.v[0] = has_l ? l2 : 0.f; ec2.v[5] = has_r ? r2 : 0.f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { ec1.v[1 + k] = av[k]; ec2.v[1 + k] = cv[k]; }
         if (i >= 2) {
             const int y = r - 1;                                // dp row: dd rows y-1, y, y+1 are in slots (i-2)%3, (i-1)%3, i%3
             if (b.live && y < H) {
                 float o[4];
-                stencil_row(e1[(i + 1) % 3], e1[(i + 2) % 3], e1[i % 3], f1, o);
+                stencil_row<true>(e1[(i + 1) % 3], e1[(i + 2) % 3], e1[i % 3], w1, o);       // 180-degree rotated filters
                 *reinterpret_cast<float4*>(o1 + (long)y * W + b.x0) = make_float4(o[0], o[1], o[2], o[3]);
-                stencil_row(e2[(i + 1) % 3], e2[(i + 2) % 3], e2[i % 3], f2, o);
+                stencil_row<true>(e2[(i + 1) % 3], e2[(i + 2) % 3], e2[i % 3], w2, o);
                 *reinterpret_cast<float4*>(o2 + (long)y * W + b.x0) = make_float4(o[0], o[1], o[2], o[3]);
             }
         }
@@ -465,20 +475,29 @@ __global__ __launch_bounds__(256) void dwconv_bwd_kernel(const float* __restrict
     // (threads per plane are a multiple of W/4): no live lane takes a halo pixel from a dead one
     if (b.live) {
         Row6 g3[3], x3[3];
-        // NB: rows are requested one iteration ahead from clamped indices and zeroed by selects when they land (see gdfn_bwd_kernel)
-        float4 ng = make_float4(0.f, 0.f, 0.f, 0.f), nx = ng;
-        auto request = [&](int y) {
-            const int yc = min(max(y, 0), H - 1);
-            ng = *reinterpret_cast<const float4*>(gp + (long)yc * W + b.x0);
-            nx = *reinterpret_cast<const float4*>(xp + (long)yc * W + b.x0);
+        // NB: the NR rows of dy and x (row k = y0 - 1 + k, slot (k + 2) % 3 of g3 / x3) are requested LA rows ahead of their use, from
+        // clamped indices, and zeroed by masks when they land (see gdfn_bwd_kernel).  A 4-row strip asks for all six before its first
+        // arithmetic: one memory round trip per strip instead of five, 13 % off the launch at 2304 planes of 64x64 for 96 registers
+        // instead of 80 (five waves per SIMD, not six); on 8-row strips two or three rows ahead measured the same as one.
+        constexpr int NR = RS + 2, LA = (NB && RS == 4) ? NR : 1;
+        float4 ng[LA], nx[LA];
+        auto request = [&](int k) {
+            const int yc = min(max(b.y0 - 1 + k, 0), H - 1);
+            ng[k % LA] = *reinterpret_cast<const float4*>(gp + (long)yc * W + b.x0);
+            nx[k % LA] = *reinterpret_cast<const float4*>(xp + (long)yc * W + b.x0);
         };
-        auto land = [&](const float4& q, int y, Row6& r) { land_row6(q, y >= 0 && y < H, has_l, has_r, r); };
+        auto land = [&](int k) {                                // the slot is free again afterwards
+            const int y = b.y0 - 1 + k;
+            const bool ok = y >= 0 && y < H;
+            land_row6(ng[k % LA], ok, has_l, has_r, g3[(k + 2) % 3]);
+            land_row6(nx[k % LA], ok, has_l, has_r, x3[(k + 2) % 3]);
+            if (k + LA < NR) request(k + LA);
+        };
         if (NB) {
-            request(b.y0 - 1);
-            land(ng, b.y0 - 1, g3[2]); land(nx, b.y0 - 1, x3[2]);
-            request(b.y0);
-            land(ng, b.y0, g3[0]); land(nx, b.y0, x3[0]);
-            request(b.y0 + 1);
+#pragma unroll
+            for (int k = 0; k < LA; ++k) request(k);
+            land(0);
+            land(1);
         } else {
             load_row6(gp, H, W, b.y0 - 1, b.x0, g3[2]);
             load_row6(xp, H, W, b.y0 - 1, b.x0, x3[2]);
@@ -492,9 +511,7 @@ __global__ __launch_bounds__(256) void dwconv_bwd_kernel(const float* __restrict
                 Row6& gu = g3[(i + 2) % 3]; Row6& gm = g3[i % 3]; Row6& gd = g3[(i + 1) % 3];
                 Row6& xu = x3[(i + 2) % 3]; Row6& xm = x3[i % 3]; Row6& xd = x3[(i + 1) % 3];
                 if (NB) {
-                    land(ng, y + 1, gd);
-                    land(nx, y + 1, xd);
-                    if (i + 1 < RS) request(y + 2);
+                    land(i + 2);
                 } else {
                     load_row6(gp, H, W, y + 1, b.x0, gd);
                     load_row6(xp, H, W, y + 1, b.x0, xd);
