@@ -25,7 +25,7 @@ extern "C" {
 
 /* Bumped on EVERY signature change; returned by rcot_abi_version() (csrc/api.hip) and compared by the loader
  * (rcot_amd/lib.py ABI_VERSION, tests/test_abi.py) so that a stale prebuilt .so is refused, not mis-called. */
-#define RCOT_ABI_VERSION 34
+#define RCOT_ABI_VERSION 35
 
 /* Arithmetic of the MFMA products of the three GEMM-shaped entry points that take `prec` (rcot_gemm_kmajor,
  * rcot_conv1x1_wgrad, rcot_bmm_nt); operands and results are fp32 in memory either way.
@@ -337,6 +337,18 @@ int rcot_attn_core_fwd(const float* u, long sUb, const float* temp, const float*
 int rcot_attn_core_bwd(const float* dM, int S, int ldd, const float* Wo, const float* A, const float* Gn, const float* sq,
                        const float* temp, float* Mf, float* dWo_part, float* dtemp_part, float* Eq, float* EqT, float* Dq, float* Dk, int B,
                        int heads, int c, void* stream);
+/* What rcot_attn_core_bwd returns, from the same arguments, on MANY workgroups: attn_rows_kernel on (row groups, heads, B)
+ * workgroups — each takes up to four consecutive 16-row tiles of W_o[:, head block] and dM[b][:, head block], one per wavefront, writes its rows of Mf and dW_o part and a partial dA to ws as [B][heads][groups][c][c] — then
+ * attn_rows_tail_kernel on (heads, B) workgroups, which adds the partials in group order and writes dtau partials, Eq, Eq^T, Dq,
+ * Dk.  Two plain launches on `stream`; same fp32 16x16x4 MFMA products.  dM: dense (S = 0) or ANY number S >= 1 of split-K slabs
+ * [B][S][C][ldd] (rcot_bmm_nt_slabs), summed while staging in slab order.  group_tiles: 0 = the launcher's rule (the C / 16 tiles spread
+ * evenly over ceil(C / 64) groups), 1 .. 4 = that many tiles per row group (the last group takes the rest; more than 4 counts as 4).  dM and Wo 16-byte, A, Gn, sq, Eq and ws 8-byte aligned (RCOT_EINVAL otherwise); ws must hold rcot_attn_rows_ws_bytes(B, heads, c,
+ * group_tiles) bytes: RCOT_EINVAL (nothing launched) when ws_bytes is smaller.  RCOT_EUNSUPPORTED as rcot_attn_core_bwd. */
+int rcot_attn_rows_bwd(const float* dM, int S, int ldd, const float* Wo, const float* A, const float* Gn, const float* sq,
+                       const float* temp, float* Mf, float* dWo_part, float* dtemp_part, float* Eq, float* EqT, float* Dq, float* Dk, int B,
+                       int heads, int c, int group_tiles, void* ws, size_t ws_bytes, void* stream);
+/* Host only: bytes of ws rcot_attn_rows_bwd needs (RCOT_EINVAL for a shape it would refuse, or 2 GiB and more). */
+int rcot_attn_rows_ws_bytes(int B, int heads, int c, int group_tiles);
 /* dst = beta*dst + sum_b src[b][0..n) */
 int rcot_batch_reduce(const float* src, float* dst, int B, long n, float beta, void* stream);
 

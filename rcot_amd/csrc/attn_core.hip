@@ -624,6 +624,364 @@ int launch_core_bwd(const float* dM, int S, long ldd, long sDs, long sDb, const 
     return RCOT_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The same backward on MANY workgroups, two launches on one stream (rcot_attn_rows_bwd).  attn_bwd_core_kernel runs on heads x B
+// workgroups (8 at the 128x128 level) and each wavefront makes C / 64 serial trips; the work is separable by rows of W and D:
+//   attn_rows_kernel       grid (row groups, heads, B): a workgroup takes `tpg` <= 4 consecutive 16-row tiles, one per wavefront,
+//                          writes its rows of Mf and dW_o part and its partial dA = W[rows]^T D[rows] to the workspace as
+//                          [b][head][group][c][c].  D is summed from the split-K slabs of dM while staging, in slab order, for any S.
+//                          The four wavefronts' shares of dA meet in LDS in ONE step (wavefront w adds rows w, w + 4, .. of all four
+//                          shares, fixed order) instead of four serialised passes.
+//   attn_rows_tail_kernel  grid (heads, B): adds the group partials in group order and does the c x c softmax backward in registers
+//                          (CT x CT elements per thread, every load requested up front, sums by lane exchange).
+// (No "last workgroup runs the tail" behind a device-scope fence: one XCD's L2 is not coherent with another's, the fence is an L2
+// write-back per workgroup — NOTES round 6 item 7.)
+template <int CT>
+struct AR {
+    using K = AB<CT>;
+    static constexpr int LDS = K::cp + 4;                           // dA shares [wave][cp][LDS]: 4 LDS == 16 (mod 64), stores hit 64 banks
+    static constexpr size_t rows = (size_t)(2 * K::cp * K::LDA + K::NW * 2 * 16 * K::LD);
+    static constexpr size_t shares = (size_t)(K::NW * K::cp * LDS);
+    static constexpr size_t smem = sizeof(float) * (rows > shares ? rows : shares);
+    static_assert(smem <= 160 * 1024, "LDS");
+};
+
+template <int CT>
+__global__ __launch_bounds__(256) void attn_rows_kernel(const float* __restrict__ dM, int S, long ldd, long sDs, long sDb,
+                                                        const float* __restrict__ Wo, const float* __restrict__ A,
+                                                        float* __restrict__ Mf, float* __restrict__ dWo_part,
+                                                        float* __restrict__ dA_part, int heads, int tpg) {
+    using K = AB<CT>;
+    constexpr int cp = K::cp, c = K::c, LDA = K::LDA, LD = K::LD, NW = K::NW, NT = K::NT, Q4 = K::Q4, NLD = K::NLD, LDS = AR<CT>::LDS;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float* As = sm;                               // A [i][j]
+    float* ATs = As + cp * LDA;                   // A^T [j][i]
+    float* tiles = ATs + cp * LDA;                // per wavefront: W tile [16][LD], D tile [16][LD]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int g = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+    const int C = heads * c;
+    const int t0 = g * tpg, t1 = min(C / 16, t0 + tpg);                 // this group's 16-row tiles (never empty: the launcher's rule)
+    const long z = (long)b * heads + h;
+    const long off = z * c * c;
+    const float* Wh = Wo + h * c;                                       // W[m][i] = Wh[m * C + i]
+    const float* Dh = dM + (long)b * sDb + h * c;                       // D[m][j] = sum_s Dh[s * sDs + m * ldd + j]
+    float* Mfh = Mf + (long)b * C * C + h * c;
+    float* dWh = dWo_part + (long)b * C * C + h * c;
+    // ---- ALL loads of a thread before its first store: A, then this wavefront's tile of W and D (wavefront w takes tile t0 + w: with
+    // one tile per wavefront there is no trip to fetch ahead for; a wavefront past the group's end loads nothing and adds zeros)
+    constexpr int NEL = (cp * cp + NT - 1) / NT;
+    float av[NEL];
+#pragma unroll
+    for (int q = 0; q < NEL; ++q) {
+        const int e = tid + q * NT;
+        const int i = e / cp, j = e - i * cp;
+        av[q] = (e < cp * cp && i < c && j < c) ? A[off + i * c + j] : 0.f;
+    }
+    const int mt = t0 + wave;
+    const bool live = mt < t1;                                           // wave-uniform
+    const float* Wm = Wh + (long)(live ? mt : t0) * 16 * C;
+    const float* Dm = Dh + (long)(live ? mt : t0) * 16 * ldd;
+    // piece q of a lane: floats 4 c4 .. 4 c4 + 3 of row r of the tile (every lane has NLD pieces except at c = 24)
+    int wo[NLD], dof[NLD];
+    f32x4 wv[NLD], dv[NLD];
+#pragma unroll
+    for (int q = 0; q < NLD; ++q) {
+        const int idx = lane + 64 * q;
+        const int r = idx / Q4, c4 = idx - r * Q4;
+        const bool ok = live && ((16 * Q4) % 64 == 0 || idx < 16 * Q4);
+        wo[q] = ok ? r * C + 4 * c4 : -1;
+        dof[q] = r * (int)ldd + 4 * c4;
+        wv[q] = ok ? *reinterpret_cast<const f32x4*>(Wm + wo[q]) : f32x4{0.f, 0.f, 0.f, 0.f};
+        dv[q] = ok ? *reinterpret_cast<const f32x4*>(Dm + dof[q]) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    // the other slabs, added in slab order, four slabs' loads in flight (S is the split factor of the dM product: 8 at the 128x128
+    // level, 16 and more on small batches); an absent slab adds zero
+#pragma unroll 1
+    for (int sl = 1; sl < S; sl += 4) {
+        f32x4 x[4][NLD];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int q = 0; q < NLD; ++q)
+                x[u][q] = (wo[q] >= 0 && sl + u < S) ? *reinterpret_cast<const f32x4*>(Dm + (long)(sl + u) * sDs + dof[q])
+                                                     : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int q = 0; q < NLD; ++q) dv[q] += x[u][q];
+    }
+#pragma unroll
+    for (int q = 0; q < NEL; ++q) {
+        const int e = tid + q * NT;
+        const int i = e / cp, j = e - i * cp;
+        if (e < cp * cp) {
+            As[i * LDA + j] = av[q];
+            ATs[j * LDA + i] = av[q];
+        }
+    }
+    const int r16 = lane & 15, kq = lane >> 4;
+    float* Wt = tiles + wave * 2 * 16 * LD;
+    float* Dt = Wt + 16 * LD;
+    // stage this wavefront's 16 rows of W and D; 8-byte LDS stores (LD is even)
+#pragma unroll
+    for (int q = 0; q < NLD; ++q) {
+        const int idx = lane + 64 * q;
+        const int r = idx / Q4, c4 = idx - r * Q4;
+        if ((16 * Q4) % 64 == 0 || idx < 16 * Q4) {
+            float* wd = Wt + r * LD + 4 * c4;
+            float* dd = Dt + r * LD + 4 * c4;
+            *reinterpret_cast<float2*>(wd) = make_float2(wv[q][0], wv[q][1]);
+            *reinterpret_cast<float2*>(wd + 2) = make_float2(wv[q][2], wv[q][3]);
+            *reinterpret_cast<float2*>(dd) = make_float2(dv[q][0], dv[q][1]);
+            *reinterpret_cast<float2*>(dd + 2) = make_float2(dv[q][2], dv[q][3]);
+        }
+    }
+    if (c < cp) {                                                        // padding columns of the tiles (c = 24)
+        for (int e = lane; e < 16 * (cp - c); e += 64) {
+            const int r = e / (cp - c), x = c + e - r * (cp - c);
+            Wt[r * LD + x] = 0.f;
+            Dt[r * LD + x] = 0.f;
+        }
+    }
+    __syncthreads();                                                     // A and A^T are complete (and every wavefront's own tile)
+    f32x4 dacc[CT][CT];
+#pragma unroll
+    for (int i = 0; i < CT; ++i)
+#pragma unroll
+        for (int j = 0; j < CT; ++j) dacc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (live) {
+        // Mf tile = W A and dW_o tile = D A^T: D[m][n], A operand lane (m = r16, k = 4 s + kq), B operand lane (k, n = r16)
+#pragma unroll 1
+        for (int nt = 0; nt < CT; ++nt) {
+            f32x4 a1 = {0.f, 0.f, 0.f, 0.f}, a2 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int s_ = 0; s_ < cp / 4; ++s_) {
+                const int k = 4 * s_ + kq;
+                a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(Wt[r16 * LD + k], As[k * LDA + 16 * nt + r16], a1, 0, 0, 0);
+                a2 = __builtin_amdgcn_mfma_f32_16x16x4f32(Dt[r16 * LD + k], ATs[k * LDA + 16 * nt + r16], a2, 0, 0, 0);
+            }
+            const int n = 16 * nt + r16;
+            if (n < c) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const long m = 16 * mt + 4 * kq + r;
+                    Mfh[m * C + n] = a1[r];
+                    dWh[m * C + n] = a2[r];
+                }
+            }
+        }
+        // dA = W^T D over the 16 rows: D[i][j], A operand lane (i = 16 it + r16, k = m = 4 s + kq), B operand lane (m, j)
+#pragma unroll
+        for (int s_ = 0; s_ < 4; ++s_) {
+            float wa[CT], db[CT];
+#pragma unroll
+            for (int t = 0; t < CT; ++t) {
+                wa[t] = Wt[(4 * s_ + kq) * LD + 16 * t + r16];
+                db[t] = Dt[(4 * s_ + kq) * LD + 16 * t + r16];
+            }
+#pragma unroll
+            for (int i = 0; i < CT; ++i)
+#pragma unroll
+                for (int j = 0; j < CT; ++j) dacc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[i], db[j], dacc[i][j], 0, 0, 0);
+        }
+    }
+    // ---- dA: the four shares side by side in LDS (over A, A^T and the tiles, which nobody reads any more), then one pass
+    __syncthreads();
+    float* sh = sm + wave * cp * LDS + (4 * kq) * LDS + r16;
+#pragma unroll
+    for (int i = 0; i < CT; ++i)
+#pragma unroll
+        for (int j = 0; j < CT; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) sh[(16 * i + r) * LDS + 16 * j] = dacc[i][j][r];
+    __syncthreads();
+    float* dp = dA_part + (z * gridDim.x + g) * c * c;
+    constexpr int NJ = (c + 63) / 64;
+#pragma unroll 2
+    for (int i = wave; i < c; i += NW) {
+#pragma unroll
+        for (int q = 0; q < NJ; ++q) {
+            const int j = lane + 64 * q;
+            if (j < c) {
+                const float* s0 = sm + i * LDS + j;
+                dp[i * c + j] = ((s0[0] + s0[cp * LDS]) + s0[2 * cp * LDS]) + s0[3 * cp * LDS];
+            }
+        }
+    }
+}
+
+// CT consecutive floats of a row (8-byte pieces where CT is even: every address here is an even number of floats from an 8-byte
+// aligned base), zeros / nothing where !ok
+template <int CT>
+__device__ __forceinline__ void row_load(float (&v)[CT], const float* __restrict__ p, bool ok) {
+    if constexpr (CT % 2 == 0) {
+#pragma unroll
+        for (int u = 0; u < CT / 2; ++u) {
+            const float2 x = ok ? *reinterpret_cast<const float2*>(p + 2 * u) : make_float2(0.f, 0.f);
+            v[2 * u] = x.x;
+            v[2 * u + 1] = x.y;
+        }
+    } else {
+#pragma unroll
+        for (int t = 0; t < CT; ++t) v[t] = ok ? p[t] : 0.f;
+    }
+}
+template <int CT>
+__device__ __forceinline__ void row_store(float* __restrict__ p, const float (&v)[CT], bool ok) {
+    if (!ok) return;
+    if constexpr (CT % 2 == 0) {
+#pragma unroll
+        for (int u = 0; u < CT / 2; ++u) *reinterpret_cast<float2*>(p + 2 * u) = make_float2(v[2 * u], v[2 * u + 1]);
+    } else {
+#pragma unroll
+        for (int t = 0; t < CT; ++t) p[t] = v[t];
+    }
+}
+
+// Sum over the 16 lanes of a DPP row, in every lane: four rotations (v_add_f32 row_ror:8 / 4 / 2 / 1) — no trip through the LDS
+// crossbar and no lgkmcnt wait, which ds_bpermute (__shfl_xor) costs per step.
+template <int CTRL>
+__device__ __forceinline__ float dpp_move(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float row16_sum(float v) {
+    v += dpp_move<0x128>(v);
+    v += dpp_move<0x124>(v);
+    v += dpp_move<0x122>(v);
+    return v + dpp_move<0x121>(v);
+}
+
+// grid (heads, B), 256 threads: thread (grp = tid >> 4, gl = tid & 15) holds the elements (i = grp + 16 rr, j = CT gl + t) of the
+// c x c block of its (head, image) in registers, rr, t < CT — 36 of the 9 216 at c = 96, six rows of six consecutive floats.  No
+// index is divided; a row's sum is a lane exchange inside its 16-lane group (row16_sum), a column's one over the four groups of a
+// wavefront (xor 16, 32) and then over the four wavefronts through 4 cp floats of LDS, in wavefront order.
+template <int CT>
+__global__ __launch_bounds__(256) void attn_rows_tail_kernel(const float* __restrict__ dA_part, int G, const float* __restrict__ A,
+                                                             const float* __restrict__ Gn, const float* __restrict__ sq,
+                                                             const float* __restrict__ temp, float* __restrict__ dtemp_part,
+                                                             float* __restrict__ Eq, float* __restrict__ EqT, float* __restrict__ Dq,
+                                                             float* __restrict__ Dk, int heads) {
+    constexpr int cp = AB<CT>::cp, c = AB<CT>::c, cc = c * c;
+    constexpr bool PAD = c < cp;                                        // c = 24: rows and columns 24 .. 31 do not exist
+    __shared__ float csw[4][cp];
+    __shared__ float red[8];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int grp = tid >> 4, gl = tid & 15;
+    const int h = blockIdx.x, b = blockIdx.y;
+    const int C = heads * c;
+    const long z = (long)b * heads + h;
+    const long off = z * cc;
+    const bool jok = !PAD || CT * gl < c;                               // (c is a multiple of CT: a lane's columns exist together)
+    const int e0 = grp * c + CT * gl;                                   // row rr of this thread starts at e0 + 16 c rr
+    // (wave-uniform bases + 32-bit lane offsets: the loads and stores take the base from SGPRs, no 64-bit address per element)
+    const float* Ah = A + off;
+    const float* Gh = Gn + off;
+    const float* Ph = dA_part + z * G * cc;
+    const float* sqq = sq + (long)b * 2 * C + h * c;
+    const float* sqk = sqq + C;
+    // ---- everything this thread reads, requested up front
+    float av[CT][CT], gv[CT][CT], d[CT][CT], q2[CT], k2[CT];
+#pragma unroll
+    for (int rr = 0; rr < CT; ++rr) {
+        const bool ok = jok && (!PAD || grp + 16 * rr < c);
+        row_load<CT>(av[rr], Ah + (e0 + 16 * c * rr), ok);
+        row_load<CT>(gv[rr], Gh + (e0 + 16 * c * rr), ok);
+        row_load<CT>(d[rr], Ph + (e0 + 16 * c * rr), ok);
+    }
+    row_load<CT>(k2, sqk + CT * gl, jok);
+#pragma unroll
+    for (int rr = 0; rr < CT; ++rr) q2[rr] = (!PAD || grp + 16 * rr < c) ? sqq[grp + 16 * rr] : 1.f;
+    const float tau = temp[h];
+    // the other groups' partials, added in group order, two groups' loads in flight; an absent group adds zero
+#pragma unroll 1
+    for (int g = 1; g < G; g += 2) {
+        float x0[CT][CT], x1[CT][CT];
+#pragma unroll
+        for (int rr = 0; rr < CT; ++rr) {
+            const bool ok = jok && (!PAD || grp + 16 * rr < c);
+            row_load<CT>(x0[rr], Ph + (long)g * cc + (e0 + 16 * c * rr), ok);
+            row_load<CT>(x1[rr], Ph + (long)(g + 1) * cc + (e0 + 16 * c * rr), ok && g + 1 < G);
+        }
+#pragma unroll
+        for (int rr = 0; rr < CT; ++rr)
+#pragma unroll
+            for (int t = 0; t < CT; ++t) d[rr][t] = (d[rr][t] + x0[rr][t]) + x1[rr][t];
+    }
+    // ---- dS = A.(dA - rowsum(dA.A)); Eq = tau dS / (|q| |k|^T) as dS (tau / |q_i|) (1 / |k_j|): 2 CT divisions, not CT^2
+    float rq[CT], rk[CT], cs[CT];
+#pragma unroll
+    for (int t = 0; t < CT; ++t) {
+        rq[t] = tau / clamp_norm(q2[t]);
+        rk[t] = jok ? 1.0f / clamp_norm(k2[t]) : 0.f;
+        cs[t] = 0.f;
+    }
+    float part = 0.f;
+    float* Eh = Eq + off;
+    float* ETh = EqT + off;
+    const int t0 = CT * gl * c + grp;                                   // Eq^T[j][i]: element (rr, t) at t0 + c t + 16 rr
+#pragma unroll
+    for (int rr = 0; rr < CT; ++rr) {
+        const bool ok = jok && (!PAD || grp + 16 * rr < c);
+        float acc = 0.f;
+#pragma unroll
+        for (int t = 0; t < CT; ++t) acc += av[rr][t] * d[rr][t];
+        acc = row16_sum(acc);
+        float rs_ = 0.f, e[CT];
+#pragma unroll
+        for (int t = 0; t < CT; ++t) {
+            const float sv = av[rr][t] * (d[rr][t] - acc);              // zero in the padding (A is)
+            const float sg = sv * gv[rr][t];
+            rs_ += sg;
+            cs[t] += sg;
+            e[t] = sv * rq[rr] * rk[t];
+            if (ok) ETh[t0 + c * t + 16 * rr] = e[t];
+        }
+        row_store<CT>(Eh + (e0 + 16 * c * rr), e, ok);
+        part += rs_;
+        rs_ = row16_sum(rs_);
+        if (gl == 0 && (!PAD || grp + 16 * rr < c)) Dq[(long)b * C + h * c + grp + 16 * rr] = q2[rr] >= 1e-24f ? -tau * rs_ / q2[rr] : 0.f;
+    }
+#pragma unroll
+    for (int t = 0; t < CT; ++t) {
+        cs[t] += __shfl_xor(cs[t], 16, 64);
+        cs[t] += __shfl_xor(cs[t], 32, 64);
+        if (lane < 16) csw[wave][CT * gl + t] = cs[t];
+    }
+    part = block_sum<256>(part, red);                                       // (its barriers also publish csw)
+    if (tid == 0) dtemp_part[z] = part;
+    if (tid < c) {
+        const float s = ((csw[0][tid] + csw[1][tid]) + csw[2][tid]) + csw[3][tid];
+        const float kk = sqk[tid];
+        Dk[(long)b * C + h * c + tid] = kk >= 1e-24f ? -tau * s / kk : 0.f;
+    }
+}
+
+// Tiles per row group: at most one per wavefront (a second one per wavefront would be a serial trip again, and C / 64 groups per
+// (head, image) fill the chip only at shapes where the kernel is no longer latency-bound).  The nmt = C / 16 tiles are spread
+// evenly over ceil(nmt / 4) groups — 6 tiles are 3 + 3, not 4 + 2 — so no group is empty.  `forced` > 0 (tests,
+// scripts/bench_attn_rows.py): that many tiles per group (at most 4), the last group takes the rest.
+inline int rows_group_tiles(int nmt, int forced) {
+    const int tpg = forced > 0 ? std::min(forced, 4) : cdiv(nmt, cdiv(nmt, 4));
+    return std::min(tpg, nmt);
+}
+
+template <int CT>
+int launch_rows_bwd(const float* dM, int S, long ldd, long sDs, long sDb, const float* Wo, const float* A, const float* Gn,
+                    const float* sq, const float* temp, float* Mf, float* dWo_part, float* dtemp_part, float* Eq, float* EqT, float* Dq,
+                    float* Dk, int B, int heads, int tpg, int G, float* dA_part, hipStream_t st) {
+    static bool once = (hipFuncSetAttribute((const void*)attn_rows_kernel<CT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            160 * 1024) == hipSuccess);
+    (void)once;
+    RCOT_LAUNCH(attn_rows_kernel<CT>, dim3(G, heads, B), dim3(256), AR<CT>::smem, st, dM, S < 1 ? 1 : S, ldd, sDs, sDb, Wo, A, Mf,
+                       dWo_part, dA_part, heads, tpg);
+    RCOT_LAUNCH_CHECK();
+    note_kernel("attn_rows_tail_kernel<%d>", CT);
+    RCOT_LAUNCH(attn_rows_tail_kernel<CT>, dim3(heads, B), dim3(256), 0, st, dA_part, G, A, Gn, sq, temp, dtemp_part, Eq, EqT, Dq,
+                       Dk, heads);
+    RCOT_LAUNCH_CHECK();
+    return RCOT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -663,6 +1021,37 @@ int rcot_attn_core_bwd(const float* dM, int S, int ldd, const float* Wo, const f
     if (c == 48) return launch_core_bwd<3>(dM, S, ldd, sDs, sDb, Wo, A, Gn, sq, temp, Mf, dWo_part, dtemp_part, Eq, EqT, Dq, Dk, B, heads, st);
     if (c == 96) return launch_core_bwd<6>(dM, S, ldd, sDs, sDb, Wo, A, Gn, sq, temp, Mf, dWo_part, dtemp_part, Eq, EqT, Dq, Dk, B, heads, st);
     return launch_core_bwd<2>(dM, S, ldd, sDs, sDb, Wo, A, Gn, sq, temp, Mf, dWo_part, dtemp_part, Eq, EqT, Dq, Dk, B, heads, st);
+}
+
+int rcot_attn_rows_ws_bytes(int B, int heads, int c, int group_tiles) {
+    if (B <= 0 || heads <= 0 || B > 65535 || heads > 65535 || group_tiles < 0 || (c != 24 && c != 48 && c != 96) || ((heads * c) % 16))
+        return RCOT_EINVAL;
+    const int nmt = heads * c / 16;
+    const long n = (long)B * heads * cdiv(nmt, rows_group_tiles(nmt, group_tiles)) * c * c * (long)sizeof(float);
+    return n > 0x7fffffffL ? RCOT_EINVAL : (int)n;
+}
+
+int rcot_attn_rows_bwd(const float* dM, int S, int ldd, const float* Wo, const float* A, const float* Gn, const float* sq,
+                       const float* temp, float* Mf, float* dWo_part, float* dtemp_part, float* Eq, float* EqT, float* Dq, float* Dk, int B,
+                       int heads, int c, int group_tiles, void* ws, size_t ws_bytes, void* stream) {
+    if (!dM || !Wo || !A || !Gn || !sq || !temp || !Mf || !dWo_part || !dtemp_part || !Eq || !EqT || !Dq || !Dk || !ws || B <= 0 ||
+        heads <= 0 || B > 65535 || heads > 65535 || S < 0 || group_tiles < 0)
+        return RCOT_EINVAL;
+    const int C = heads * c;
+    if ((C % 16) || (c != 24 && c != 48 && c != 96)) return RCOT_EUNSUPPORTED;
+    if (S == 0) ldd = C;
+    auto al8 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; };     // the tail moves 8-byte pieces
+    if (ldd < C || (ldd & 3) || !al16(dM) || !al16(Wo) || !al8(A) || !al8(Gn) || !al8(sq) || !al8(Eq) || !al8(ws)) return RCOT_EINVAL;
+    const int nmt = C / 16, tpg = rows_group_tiles(nmt, group_tiles), G = cdiv(nmt, tpg);
+    if ((size_t)B * heads * G * c * c * sizeof(float) > ws_bytes) return RCOT_EINVAL;        // the partial dA blocks
+    const long sDs = (long)C * ldd, sDb = (long)(S < 1 ? 1 : S) * sDs;
+    hipStream_t st = (hipStream_t)stream;
+    float* part = static_cast<float*>(ws);
+    if (c == 48)
+        return launch_rows_bwd<3>(dM, S, ldd, sDs, sDb, Wo, A, Gn, sq, temp, Mf, dWo_part, dtemp_part, Eq, EqT, Dq, Dk, B, heads, tpg, G, part, st);
+    if (c == 96)
+        return launch_rows_bwd<6>(dM, S, ldd, sDs, sDb, Wo, A, Gn, sq, temp, Mf, dWo_part, dtemp_part, Eq, EqT, Dq, Dk, B, heads, tpg, G, part, st);
+    return launch_rows_bwd<2>(dM, S, ldd, sDs, sDb, Wo, A, Gn, sq, temp, Mf, dWo_part, dtemp_part, Eq, EqT, Dq, Dk, B, heads, tpg, G, part, st);
 }
 
 }  // extern "C"

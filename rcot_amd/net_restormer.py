@@ -275,18 +275,25 @@ class TransformerBlockOp:
         # ---- MDTA
         Q, K, V = self._qkv_views(u)
         dy4 = dy.view(B, 1, C, N)
-        dM, Mf = be.empty(B, C, C), be.empty(B, C, C)
-        # (rcot_attn_core_bwd also takes dM as the <= 8 split-K slabs of rcot_bmm_nt_slabs and sums them while staging; wired in for the
-        # 32x32 / 16x16 planes in round 5 it removed a reduce launch and NO time — 340.0 vs 341.0 us per 16x16 block backward,
-        # profiles/r05_ab_small_levels.txt — while the split factor depends on the batch (16 at B = 2): not kept in the schedule)
-        be.bmm_nt(dy4, V, dM.unsqueeze(1))                           # dM = dY V^T
+        Mf = be.empty(B, C, C)
+        # dM = dY V^T.  Where the row-group form of the backward runs (HipBackend.attn_rows_route) on a plane of at most
+        # attn_rows_slab_maxn pixels it stays the split-K slabs of the product: that form sums any number of them while it stages
+        # its rows, so the reduce launch goes.  Larger planes split 64 ways: summing that many is the reduce launch's work.
+        # (rcot_attn_core_bwd also takes <= 8 slabs; wired in for the 32x32 / 16x16 planes in round 5 it removed a reduce launch and
+        # NO time — 340.0 vs 341.0 us per 16x16 block backward, profiles/r05_ab_small_levels.txt — while the split factor depends on
+        # the batch (16 at B = 2): not kept in the schedule)
+        rows = getattr(be, "attn_rows_route", None)
+        dM = be.bmm_nt_slabs(dy4, V) if rows is not None and rows(c, hd) and N <= be.attn_rows_slab_maxn else None
+        if dM is None:
+            dM = be.empty(B, C, C)
+            be.bmm_nt(dy4, V, dM.unsqueeze(1))
         du = be.empty(B, 3 * C, H, W)
         dQ, dK, dV = self._qkv_views(du)
         dWo_part, dtemp_part = be.empty(B, C, C), be.empty(B, hd)
         Eq, EqT = be.empty(B, hd, c, c), be.empty(B, hd, c, c)
         Dq, Dk = be.empty(B, C), be.empty(B, C)
         if be.attn_core_bwd(dM, self.Wo, A, Gn, sq, self.temp, Mf, dWo_part, dtemp_part, Eq, EqT, Dq, Dk):
-            pass        # Mf = W_o blockdiag(A), dW_o (per image), dA = W_o^T dM and the softmax backward: ONE launch, fp32 MFMA
+            pass        # Mf = W_o blockdiag(A), dW_o (per image), dA = W_o^T dM and the softmax backward: fp32 MFMA, row groups + tail or ONE launch
         elif be.attn_fused_ok(c):
             # the same as two launches (row chunks, then the c x c tail)
             be.attn_bwd_fused(dM, self.Wo, A, Gn, sq, self.temp, Mf, dWo_part, dtemp_part, Eq, EqT, Dq, Dk)

@@ -1142,23 +1142,61 @@ class HipBackend:
                                               Eq.data_ptr(), EqT.data_ptr(), Dq.data_ptr(), Dk.data_ptr(), B, heads, c,
                                               self.ws.data_ptr(), self.ws_bytes, self._st()), "rcot_attn_bwd_fused")
 
-    def attn_core_bwd(self, dM, Wo, A, Gn, sq, temp, Mf, dWo_part, dtemp_part, Eq, EqT, Dq, Dk) -> bool:
-        """Everything attn_bwd_fused returns, in ONE launch (rcot_attn_core_bwd).  ``dM``: the dense [B, C, C] tensor or the slab
-        descriptor (pointer, S <= 8, ld) of bmm_nt_slabs.  False when there is no such kernel for the head width."""
-        B, heads, c, _ = A.shape
-        if c > 48:
-            # c = 96 (decoder_level1 / refinement / noise_level3): measured equal or slower than the two-launch form (57.8 vs 57 us
-            # at the 128x128 level, 93 vs 84 us at 16x16): one workgroup per (head, image) walks 4x the MFMA work alone
+    # "auto": the measured rule of attn_rows_route(); "on" / "off": every head width / none (tests and scripts/bench_attn_rows.py
+    # compare the two forms through this wrapper)
+    attn_rows = "auto"
+    # planes up to this many pixels hand dM = dY V^T to the row-group form as the split-K slabs of the product (no reduce launch).
+    # A wavefront adds the slabs of its 16 rows alone, four loads deep: fine for the 4 .. 16 slabs of a reduction over <= 1024 pixels
+    # (rcot_bmm_nt_slabs splits at most K / 64 ways), not for the 64 of the 64x64 and 128x128 planes (attn_rows_kernel<6> 32.9 us with
+    # 64 slabs at 128x128) — there the reduce launch (4.3 - 4.9 us on a thousand workgroups) stays
+    attn_rows_slab_maxn = 1024
+
+    def attn_rows_route(self, c: int, heads: int) -> bool:
+        """Whether attn_core_bwd() takes the row-group form (rcot_attn_rows_bwd: row groups on many workgroups + a c x c tail) for
+        this head width and count; TransformerBlockOp.backward then hands dM over as the slabs of bmm_nt_slabs."""
+        if c not in (24, 48, 96) or (heads * c) % 16:                   # (what rcot_attn_rows_bwd refuses)
             return False
+        if self.attn_rows != "auto":
+            return self.attn_rows == "on"
+        # Measured at B = 8, exact fp32 (profiles/attn_rows_bwd.txt; kernels behind their own dM product / one block backward from a
+        # launch plan, us, old -> row groups):
+        #   c = 96, 1 head,  128x128:  50.9 -> 30.2   /  998 -> 984      c = 96, 4 heads, 16x16:  92.4 -> 33.6   /  358 -> 300
+        #   c = 48, 2 heads, 64x64:    20.6 -> 14.8   /  331 -> 327      c = 48, 4 heads, 32x32:  22.9 -> 12.3   /  294 -> 280
+        #   c = 48, 8 heads, 16x16:    34.3 -> 18.4   /  301 -> 287      c = 48, 1 head,  128x128: 17.6 -> 14.1  /  452 -> 452
+        # c = 96 always.  c = 48 from two heads on: with one head (C = 48, the 128x128 encoder / decoder level) the three row tiles
+        # are ONE row group — the same 8 workgroups as the one-launch form plus a second launch, nothing in the block.  c = 24
+        # (two block applications per step) was not measured: it stays on the one-launch form.
+        return c == 96 or (c == 48 and heads >= 2)
+
+    def attn_core_bwd(self, dM, Wo, A, Gn, sq, temp, Mf, dWo_part, dtemp_part, Eq, EqT, Dq, Dk) -> bool:
+        """Everything attn_bwd_fused returns, from rcot_attn_rows_bwd (two launches on many workgroups) where attn_rows_route()
+        says so, else in ONE launch (rcot_attn_core_bwd).  ``dM``: the dense [B, C, C] tensor or the slab descriptor (pointer, S,
+        ld) of bmm_nt_slabs (any S for the row-group form, S <= 8 for the one-launch form).  False when neither takes the shape."""
+        B, heads, c, _ = A.shape
         for t in (Wo, A, Gn, sq, temp, Mf, dWo_part, dtemp_part, Eq, EqT, Dq, Dk):
             assert t.is_contiguous()
         if isinstance(dM, tuple):
             dp, S, ld = dM
-            if S > 8:
-                return False
         else:
             assert dM.is_contiguous()
             dp, S, ld = dM.data_ptr(), 0, heads * c
+        if self.attn_rows_route(c, heads):
+            # the row-group form (rcot_attn_rows_bwd): its partial dA blocks go into this stream's workspace BEHIND the slabs of dM
+            # where those lie in it (both are dead once the call's second launch has run; the side stream has a workspace of its own)
+            C_ = heads * c
+            ws0, used = self.ws.data_ptr(), 0
+            if S > 0 and ws0 <= dp < ws0 + self.ws_bytes:
+                used = -(-(dp - ws0 + 4 * B * S * C_ * ld) // 256) * 256
+            rc = self.L.rcot_attn_rows_bwd(dp, S, ld, Wo.data_ptr(), A.data_ptr(), Gn.data_ptr(), sq.data_ptr(), temp.data_ptr(),
+                                           Mf.data_ptr(), dWo_part.data_ptr(), dtemp_part.data_ptr(), Eq.data_ptr(), EqT.data_ptr(),
+                                           Dq.data_ptr(), Dk.data_ptr(), B, heads, c, 0, ws0 + used, max(self.ws_bytes - used, 0),
+                                           self._st())
+            if rc == _lib.EUNSUPPORTED:
+                return False
+            _lib.check(rc, "rcot_attn_rows_bwd")
+            return True
+        if c > 48 or S > 8:
+            return False
         rc = self.L.rcot_attn_core_bwd(dp, S, ld, Wo.data_ptr(), A.data_ptr(), Gn.data_ptr(), sq.data_ptr(), temp.data_ptr(),
                                        Mf.data_ptr(), dWo_part.data_ptr(), dtemp_part.data_ptr(), Eq.data_ptr(), EqT.data_ptr(),
                                        Dq.data_ptr(), Dk.data_ptr(), B, heads, c, self._st())

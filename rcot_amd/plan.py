@@ -28,7 +28,7 @@ import torch
 
 from . import lib as _lib
 
-_HOST_ONLY = {"rcot_abi_version", "rcot_debug_nt_coop", "rcot_ln_bwd_rows", "rcot_last_kernel", "rcot_kmajor_desc_size", "rcot_profile_begin", "rcot_profile_end", "rcot_fft_plan"}          # no launch, no stream argument
+_HOST_ONLY = {"rcot_abi_version", "rcot_debug_nt_coop", "rcot_ln_bwd_rows", "rcot_last_kernel", "rcot_kmajor_desc_size", "rcot_profile_begin", "rcot_profile_end", "rcot_fft_plan", "rcot_attn_rows_ws_bytes"}          # no launch, no stream argument
 
 
 class _RecordingLib:
