@@ -333,13 +333,10 @@ int launch_core_fwd(const float* u, long sUb, const float* temp, const float* Wo
                     long ldm, long sMb, int B, int heads, int c, int N, float* ws, size_t ws_bytes, hipStream_t st) {
     using K = AC<CT>;
     const int C = heads * c;
-    static bool once = (hipFuncSetAttribute((const void*)qk_stats_kernel<CT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) ==
-                        hipSuccess);
-    (void)once;
     const int ms = cdiv(C / 16, K::MT_WG);                         // column slices of the fold
     if (N == 256 && CT != 6) {                                     // one launch: every slice workgroup takes the statistics itself
-        RCOT_LAUNCH(qk_stats_kernel<CT>, dim3(ms, heads, B), dim3(K::NT), K::smem_stats, st, u, sUb, heads, N, N, nullptr,
-                           nullptr, temp, WoT, ldwt, sq, Gn, A, MfT, ldm, sMb);
+        launch_lds<qk_stats_kernel<CT>>(dim3(ms, heads, B), dim3(K::NT), K::smem_stats, st, u, sUb, heads, N, N, nullptr, nullptr, temp,
+                                        WoT, ldwt, sq, Gn, A, MfT, ldm, sMb);
         RCOT_LAUNCH_CHECK();
         return RCOT_OK;
     }
@@ -352,8 +349,8 @@ int launch_core_fwd(const float* u, long sUb, const float* temp, const float* Wo
     if (!ws || ws_bytes < need) return RCOT_EWORKSPACE;
     float* gpart = ws;
     float* sqpart = ws + Z * S * c * c;
-    RCOT_LAUNCH(qk_stats_kernel<CT>, dim3(S, heads, B), dim3(K::NT), K::smem_stats, st, u, sUb, heads, N, pxw, gpart, sqpart,
-                       temp, WoT, ldwt, sq, Gn, A, MfT, ldm, sMb);
+    launch_lds<qk_stats_kernel<CT>>(dim3(S, heads, B), dim3(K::NT), K::smem_stats, st, u, sUb, heads, N, pxw, gpart, sqpart, temp, WoT,
+                                    ldwt, sq, Gn, A, MfT, ldm, sMb);
     RCOT_LAUNCH_CHECK();
     RCOT_LAUNCH(softmax_fold_kernel<CT>, dim3(ms, heads, B), dim3(K::NT), K::smem_fold, st, gpart, sqpart, S, heads, temp, WoT,
                        ldwt, sq, Gn, A, MfT, ldm, sMb);
@@ -615,11 +612,8 @@ int launch_core_bwd(const float* dM, int S, long ldd, long sDs, long sDb, const 
                     const float* sq, const float* temp, float* Mf, float* dWo_part, float* dtemp_part, float* Eq, float* EqT, float* Dq,
                     float* Dk, int B, int heads, hipStream_t st) {
     using K = AB<CT>;
-    static bool once = (hipFuncSetAttribute((const void*)attn_bwd_core_kernel<CT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            160 * 1024) == hipSuccess);
-    (void)once;
-    RCOT_LAUNCH(attn_bwd_core_kernel<CT>, dim3(heads, B), dim3(K::NT), K::smem, st, dM, S < 1 ? 1 : S, ldd, sDs, sDb, Wo, A, Gn, sq,
-                       temp, Mf, dWo_part, dtemp_part, Eq, EqT, Dq, Dk, heads);
+    launch_lds<attn_bwd_core_kernel<CT>>(dim3(heads, B), dim3(K::NT), K::smem, st, dM, S < 1 ? 1 : S, ldd, sDs, sDb, Wo, A, Gn, sq, temp,
+                                         Mf, dWo_part, dtemp_part, Eq, EqT, Dq, Dk, heads);
     RCOT_LAUNCH_CHECK();
     return RCOT_OK;
 }
@@ -969,11 +963,8 @@ template <int CT>
 int launch_rows_bwd(const float* dM, int S, long ldd, long sDs, long sDb, const float* Wo, const float* A, const float* Gn,
                     const float* sq, const float* temp, float* Mf, float* dWo_part, float* dtemp_part, float* Eq, float* EqT, float* Dq,
                     float* Dk, int B, int heads, int tpg, int G, float* dA_part, hipStream_t st) {
-    static bool once = (hipFuncSetAttribute((const void*)attn_rows_kernel<CT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            160 * 1024) == hipSuccess);
-    (void)once;
-    RCOT_LAUNCH(attn_rows_kernel<CT>, dim3(G, heads, B), dim3(256), AR<CT>::smem, st, dM, S < 1 ? 1 : S, ldd, sDs, sDb, Wo, A, Mf,
-                       dWo_part, dA_part, heads, tpg);
+    launch_lds<attn_rows_kernel<CT>>(dim3(G, heads, B), dim3(256), AR<CT>::smem, st, dM, S < 1 ? 1 : S, ldd, sDs, sDb, Wo, A, Mf,
+                                     dWo_part, dA_part, heads, tpg);
     RCOT_LAUNCH_CHECK();
     note_kernel("attn_rows_tail_kernel<%d>", CT);
     RCOT_LAUNCH(attn_rows_tail_kernel<CT>, dim3(heads, B), dim3(256), 0, st, dA_part, G, A, Gn, sq, temp, dtemp_part, Eq, EqT, Dq,

@@ -306,12 +306,9 @@ int rcot_attn_bwd_small(const float* dA, const float* A, const float* Gn, const 
     if (!dA || !A || !Gn || !sq || !temp || !dtemp_part || !Eq || !EqT || !Dq || !Dk || B <= 0 || heads <= 0 || c <= 0 ||
         c > CMAX || B > 65535)
         return RCOT_EINVAL;
-    static bool once = (hipFuncSetAttribute((const void*)attn_bwd_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            160 * 1024) == hipSuccess);
-    (void)once;
     const size_t smem = sizeof(float) * (3 * CMAX * LDA + 4);
-    RCOT_LAUNCH(attn_bwd_small_kernel, dim3(heads, B), dim3(256), smem, (hipStream_t)stream, dA, A, Gn, sq, temp,
-                       dtemp_part, Eq, EqT, Dq, Dk, heads, c, 1);
+    launch_lds<attn_bwd_small_kernel>(dim3(heads, B), dim3(256), smem, (hipStream_t)stream, dA, A, Gn, sq, temp, dtemp_part, Eq, EqT, Dq,
+                                      Dk, heads, c, 1);
     RCOT_LAUNCH_CHECK();
     return RCOT_OK;
 }
@@ -329,35 +326,19 @@ int rcot_attn_bwd_fused(const float* dM, const float* Wo, const float* A, const 
     float* dA_part = static_cast<float*>(ws);
     const size_t smem = sizeof(float) * ((size_t)c * LD + 2 * R * LD);
     const dim3 grid(heads, B, nch);
-    if (c == 48) {
-        static bool once = (hipFuncSetAttribute((const void*)attn_bwd_chunk_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                160 * 1024) == hipSuccess);
-        (void)once;
-        RCOT_LAUNCH(attn_bwd_chunk_kernel<3>, grid, dim3(256), smem, (hipStream_t)stream, dM, Wo, A, Mf, dWo_part, dA_part,
-                           heads);
-    } else {
-        static bool once = (hipFuncSetAttribute((const void*)attn_bwd_chunk_kernel<6>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                160 * 1024) == hipSuccess);
-        (void)once;
-        RCOT_LAUNCH(attn_bwd_chunk_kernel<6>, grid, dim3(256), smem, (hipStream_t)stream, dM, Wo, A, Mf, dWo_part, dA_part,
-                           heads);
-    }
+    if (c == 48) launch_lds<attn_bwd_chunk_kernel<3>>(grid, dim3(256), smem, (hipStream_t)stream, dM, Wo, A, Mf, dWo_part, dA_part, heads);
+    else launch_lds<attn_bwd_chunk_kernel<6>>(grid, dim3(256), smem, (hipStream_t)stream, dM, Wo, A, Mf, dWo_part, dA_part, heads);
     RCOT_LAUNCH_CHECK();
-    static bool once2 = (hipFuncSetAttribute((const void*)attn_bwd_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             160 * 1024) == hipSuccess);
-    (void)once2;
     const size_t smem2 = sizeof(float) * (3 * CMAX * LDA + 4);
-    RCOT_LAUNCH(attn_bwd_small_kernel, dim3(heads, B), dim3(256), smem2, (hipStream_t)stream, dA_part, A, Gn, sq, temp,
-                       dtemp_part, Eq, EqT, Dq, Dk, heads, c, nch);
+    launch_lds<attn_bwd_small_kernel>(dim3(heads, B), dim3(256), smem2, (hipStream_t)stream, dA_part, A, Gn, sq, temp, dtemp_part, Eq, EqT,
+                                      Dq, Dk, heads, c, nch);
     RCOT_LAUNCH_CHECK();
     return RCOT_OK;
 }
 
 int rcot_batch_reduce(const float* src, float* dst, int B, long n, float beta, void* stream) {
     if (!src || !dst || B <= 0 || n <= 0) return RCOT_EINVAL;
-    long g = (n + 255) / 256;
-    if (g > 4096) g = 4096;
-    RCOT_LAUNCH(batch_reduce_kernel, dim3((int)g), dim3(256), 0, (hipStream_t)stream, src, dst, B, n, beta);
+    RCOT_LAUNCH(batch_reduce_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, (hipStream_t)stream, src, dst, B, n, beta);
     RCOT_LAUNCH_CHECK();
     return RCOT_OK;
 }

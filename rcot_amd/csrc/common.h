@@ -37,6 +37,16 @@ template <typename F> inline const void* prof_fn(F f) { return reinterpret_cast<
 
 namespace rcot {
 
+// Launch of a kernel whose dynamic LDS may pass the 64 KiB a kernel gets by default: the limit is raised to the CU's 160 KiB once per
+// kernel (one instantiation of this template, and so one `once`, per kernel), then RCOT_LAUNCH.  The caller checks with
+// RCOT_LAUNCH_CHECK() as after any launch.
+template <auto Kernel, class... A>
+inline void launch_lds(dim3 grid, dim3 block, size_t smem, hipStream_t st, const A&... a) {
+    static bool once = (hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess);
+    (void)once;
+    RCOT_LAUNCH(Kernel, grid, block, smem, st, a...);
+}
+
 constexpr int WAVE = 64;
 
 __device__ __forceinline__ float wave_sum(float v) {

@@ -623,20 +623,7 @@ int launch_conv_dgrad_lean(GemmDims d, const float* Wt, const ConvGeom& g, const
     RCOT_LAUNCH((conv_dgrad_lean_kernel<S2>), dim3(d.tilesM * d.tilesN, 1, Z * d.S), dim3(256), 0, st, d, Wt, g, epv);
     RCOT_LAUNCH_CHECK();
     if (d.S > 1) {
-        const long total = (long)d.M * d.N * Z;
-        if (d.S <= 8 && reduce4_ok(d, ep, Z)) {
-            long nb = (total / 4 + 255) / 256;
-            if (nb > 8192) nb = 8192;
-            RCOT_LAUNCH(splitk_reduce_few4_kernel, dim3((int)nb), dim3(256), 0, st, d, ep, Z);
-        } else if (d.S <= 8) {
-            long nb = (total + 255) / 256;
-            if (nb > 8192) nb = 8192;
-            RCOT_LAUNCH(splitk_reduce_few_kernel, dim3((int)nb), dim3(256), 0, st, d, ep, Z);
-        } else {
-            long nb = (total + 63) / 64;
-            if (nb > 8192) nb = 8192;
-            RCOT_LAUNCH(splitk_reduce_kernel, dim3((int)nb), dim3(256), 0, st, d, ep, Z);
-        }
+        launch_splitk_reduce(d, ep, Z, st);
         RCOT_LAUNCH_CHECK();
     }
     return RCOT_OK;
@@ -838,20 +825,7 @@ int launch_conv_wgrad_lean(GemmDims d, const float* dY, const ConvGeom& g, const
     else RCOT_LAUNCH((conv_wgrad_lean_kernel<0>), grid, dim3(256), 0, st, d, dY, g, epv);
     RCOT_LAUNCH_CHECK();
     if (d.S > 1) {
-        const long total = (long)d.M * d.N;
-        if (d.S <= 8 && reduce4_ok(d, ep, 1)) {
-            long nb = (total / 4 + 255) / 256;
-            if (nb > 8192) nb = 8192;
-            RCOT_LAUNCH(splitk_reduce_few4_kernel, dim3((int)nb), dim3(256), 0, st, d, ep, 1);
-        } else if (d.S <= 8) {
-            long nb = (total + 255) / 256;
-            if (nb > 8192) nb = 8192;
-            RCOT_LAUNCH(splitk_reduce_few_kernel, dim3((int)nb), dim3(256), 0, st, d, ep, 1);
-        } else {
-            long nb = (total + 63) / 64;
-            if (nb > 8192) nb = 8192;
-            RCOT_LAUNCH(splitk_reduce_kernel, dim3((int)nb), dim3(256), 0, st, d, ep, 1);
-        }
+        launch_splitk_reduce(d, ep, 1, st);
         RCOT_LAUNCH_CHECK();
     }
     return RCOT_OK;
@@ -875,33 +849,10 @@ int launch_conv_fwd_lean(GemmDims d, const float* Wt, const ConvGeom& g, const E
     else RCOT_LAUNCH((conv_fwd_lean_kernel<1>), dim3(d.tilesM * d.tilesN, 1, d.S), dim3(256), 0, st, d, Wt, g, epv);
     RCOT_LAUNCH_CHECK();
     if (d.S > 1) {
-        const long total = (long)d.M * d.N;
-        if (d.S <= 8 && reduce4_ok(d, ep, 1)) {
-            long nb = (total / 4 + 255) / 256;
-            if (nb > 8192) nb = 8192;
-            RCOT_LAUNCH(splitk_reduce_few4_kernel, dim3((int)nb), dim3(256), 0, st, d, ep, 1);
-        } else if (d.S <= 8) {
-            long nb = (total + 255) / 256;
-            if (nb > 8192) nb = 8192;
-            RCOT_LAUNCH(splitk_reduce_few_kernel, dim3((int)nb), dim3(256), 0, st, d, ep, 1);
-        } else {
-            long nb = (total + 63) / 64;
-            if (nb > 8192) nb = 8192;
-            RCOT_LAUNCH(splitk_reduce_kernel, dim3((int)nb), dim3(256), 0, st, d, ep, 1);
-        }
+        launch_splitk_reduce(d, ep, 1, st);
         RCOT_LAUNCH_CHECK();
     }
     return RCOT_OK;
-}
-
-// tile + split-K plan shared by the three conv GEMMs
-void plan_conv(GemmDims& d, int Z, float* ws, size_t ws_bytes, bool& big) {
-    LaunchPlan pl = plan_gemm(d.M, d.N, d.K, Z, ws != nullptr, ws_bytes);
-    big = pl.big;
-    d.S = pl.S;
-    d.kchunk = cdiv(cdiv(d.K, d.S), BK) * BK;
-    d.S = cdiv(d.K, d.kchunk);
-    d.ws = ws;
 }
 
 bool dgrad_lean() {
@@ -946,15 +897,14 @@ int rcot_conv2d_fwd(const float* X, const float* Wt, const float* bias, float* Y
                         (long)Co * d.K < (1L << 29) && KH * KW <= 31 && KW <= 7;
     if (lean_f && conv_rows80(Co)) {          // ONE row tile per 64 pixels (the 16-row form): the split factor is planned for that grid —
         d.M = 64;                             // planned as two tiles of 128 pixels, the 80-channel level at 4 x 128 x 128 split in two
-        plan_conv(d, 1, ws, ws_bytes, big);   // for nothing (94 -> 85 us, and no reduce launch behind it)
+        big = plan_splitk(d, 1, ws, ws_bytes);   // for nothing (94 -> 85 us, and no reduce launch behind it)
         d.M = Co;
         while (d.S > 1 && (size_t)d.M * d.N * d.S * sizeof(float) > ws_bytes) {
             --d.S;
-            d.kchunk = cdiv(cdiv(d.K, d.S), BK) * BK;
-            d.S = cdiv(d.K, d.kchunk);
+            cut_k(d);
         }
     } else {
-        plan_conv(d, 1, ws, ws_bytes, big);
+        big = plan_splitk(d, 1, ws, ws_bytes);
     }
     if (d.S > 1 && (size_t)d.M * d.N * d.S * sizeof(float) > ws_bytes) return RCOT_EWORKSPACE;
     // the lean 64x64 kernel takes every shape it can (same split plan, so results do not depend on which kernel ran); RCOT_CONV_LEAN=0:
@@ -990,7 +940,7 @@ int rcot_conv2d_dgrad(const float* dY, const float* Wt, float* dX, int B, int Ci
         const int P2 = (H >> 1) * (W >> 1);
         d.N = B * P2; d.K = Co * 4;
         ep.cmap = 3; ep.mapH = H >> 1; ep.mapW = W >> 1; ep.foldP.init(P2);
-        plan_conv(d, 4, ws, ws_bytes, big);
+        big = plan_splitk(d, 4, ws, ws_bytes);
         if (d.S > 1 && (size_t)d.M * d.N * 4 * d.S * sizeof(float) > ws_bytes) return RCOT_EWORKSPACE;
         if (dgrad_lean() && (long)B * Co * gb.OH * gb.OW < (1L << 29) && (long)Co * Ci * 16 < (1L << 29))
             return launch_conv_dgrad_lean<true>(d, Wt, gb, ep, (hipStream_t)stream);
@@ -999,7 +949,7 @@ int rcot_conv2d_dgrad(const float* dY, const float* Wt, float* dX, int B, int Ci
     }
     d.N = B * H * W; d.K = Co * KH * KW;
     ep.ldc = (long)H * W; ep.foldP.init(H * W);
-    plan_conv(d, 1, ws, ws_bytes, big);
+    big = plan_splitk(d, 1, ws, ws_bytes);
     if (d.S > 1 && (size_t)d.M * d.N * d.S * sizeof(float) > ws_bytes) return RCOT_EWORKSPACE;
     if (dgrad_lean() && (long)B * Co * gb.OH * gb.OW < (1L << 29) && (long)Co * Ci * KH * KW < (1L << 29) && KH * KW <= 31 && KW <= 7)
         return launch_conv_dgrad_lean<false>(d, Wt, gb, ep, (hipStream_t)stream);
@@ -1023,15 +973,14 @@ int rcot_conv2d_wgrad(const float* dY, const float* X, float* dWt, int B, int Ci
     const bool lean_w = dgrad_lean() && gb.OH * gb.OW >= 16 && (long)B * Ci * H * W < (1L << 29) && (long)B * Co * gb.OH * gb.OW < (1L << 29);
     if (lean_w && conv_rows80(Co)) {          // one row tile instead of two: the split factor is planned for that grid
         d.M = 64;
-        plan_conv(d, 1, ws, ws_bytes, big);
+        big = plan_splitk(d, 1, ws, ws_bytes);
         d.M = Co;
         while (d.S > 1 && (size_t)d.M * d.N * d.S * sizeof(float) > ws_bytes) {
             --d.S;
-            d.kchunk = cdiv(cdiv(d.K, d.S), BK) * BK;
-            d.S = cdiv(d.K, d.kchunk);
+            cut_k(d);
         }
     } else {
-        plan_conv(d, 1, ws, ws_bytes, big);
+        big = plan_splitk(d, 1, ws, ws_bytes);
     }
     if (d.S > 1 && (size_t)d.M * d.N * d.S * sizeof(float) > ws_bytes) return RCOT_EWORKSPACE;
     EpiP ep{};

@@ -838,6 +838,51 @@ inline bool epi_vec_ok(const EpiP& e, int N) {
     return true;
 }
 
+// The engine's split-K cut: K in pieces of whole BK tiles, at most S of them (d.S is the wanted count on entry, the real one after).
+inline void cut_k(GemmDims& d) {
+    d.kchunk = cdiv(cdiv(d.K, d.S), BK) * BK;
+    d.S = cdiv(d.K, d.kchunk);
+}
+
+// Sum of the engine's d.S split-K slabs into the output (call when d.S > 1): three kernels of ONE summation order
+// (splitk_reduce_few_kernel above), chosen by the slab count and by what the 16-byte form can store.
+inline void launch_splitk_reduce(const GemmDims& d, const EpiP& ep, int Z, hipStream_t st) {
+    const long total = (long)d.M * d.N * Z;
+    if (d.S <= 8 && reduce4_ok(d, ep, Z))
+        RCOT_LAUNCH(splitk_reduce_few4_kernel, dim3(grid_for(total / 4)), dim3(256), 0, st, d, ep, Z);
+    else if (d.S <= 8)
+        RCOT_LAUNCH(splitk_reduce_few_kernel, dim3(grid_for(total)), dim3(256), 0, st, d, ep, Z);
+    else
+        RCOT_LAUNCH(splitk_reduce_kernel, dim3(grid_for(total, 64)), dim3(256), 0, st, d, ep, Z);
+}
+
+// The split-K cut of the slab-ring kernels (gemm_x3_kernel, x3p_kernel): nk slabs of BK in at most `want` pieces of >= 8 slabs whose
+// partial products (set_bytes for one piece of every tile) fit the workspace; the ring needs two slabs in every piece.  Whether to split
+// at all, and into how many pieces, is the caller's own fill rule (want = 1: no split); base = output tiles of the launch.
+struct SlabCut {
+    int S, kchunk, ntiles;
+    // every workgroup gets the same number of tiles (+-1): grid = tiles / rounds
+    int grid(int slots) const { return cdiv(ntiles, cdiv(ntiles, slots)); }
+};
+inline SlabCut cut_slabs(int nk, int base, int want, size_t set_bytes, size_t ws_bytes) {
+    int S = want;
+    if (S > nk / 8) S = nk / 8;
+    while (S > 1 && (size_t)S * set_bytes > ws_bytes) --S;
+    if (S < 1) S = 1;
+    SlabCut c;
+    c.kchunk = cdiv(nk, S);
+    c.S = cdiv(nk, c.kchunk);
+    if (c.S > 1 && nk - (c.S - 1) * c.kchunk < 2) {
+        c.kchunk = cdiv(nk, c.S - 1);
+        c.S = cdiv(nk, c.kchunk);
+    }
+    c.ntiles = base * c.S;
+    return c;
+}
+
+// grid of the slab-ring kernels' 16-bytes-per-thread reduce launches (x3_reduce_kernel, x3w_reduce_kernel, x3w_conv_reduce_kernel)
+inline int slab_reduce_grid(int M, int N) { return grid_for((long)M * (N / 4), 256, 2048); }
+
 struct LaunchPlan {
     bool big;      // 128x128 tile (else 64x64)
     int S;
@@ -869,6 +914,16 @@ inline LaunchPlan plan_gemm(int M, int N, int K, int Z, bool allow_split, size_t
     return p;
 }
 
+// Tile and split-K plan of one product on the engine (the general GEMMs and the three convolution GEMMs): d.S, d.kchunk and d.ws;
+// returns whether the 128x128 tile is planned.  No workspace, no split.
+inline bool plan_splitk(GemmDims& d, int Z, float* ws, size_t ws_bytes) {
+    const LaunchPlan pl = plan_gemm(d.M, d.N, d.K, Z, ws != nullptr, ws_bytes);
+    d.S = pl.S;
+    cut_k(d);
+    d.ws = ws;
+    return pl.big;
+}
+
 template <class Cfg, class AL, class AP, class BL, class BP, bool GEN = false>
 inline int launch_gemm_cfg(GemmDims d, const AP& ap, const BP& bp, const EpiP& ep, int Z, hipStream_t st) {
     if (!GEN && (ep.bias || ep.lrelu != 1.f || ep.transC || ep.cmap || ep.fold)) return RCOT_EINVAL;
@@ -881,20 +936,7 @@ inline int launch_gemm_cfg(GemmDims d, const AP& ap, const BP& bp, const EpiP& e
     RCOT_LAUNCH((gemm_kernel<Cfg, AL, AP, BL, BP, GEN>), grid, dim3(GEMM_NT), 0, st, d, ap, bp, epv);
     RCOT_LAUNCH_CHECK();
     if (d.S > 1) {
-        const long total = (long)d.M * d.N * Z;
-        if (d.S <= 8 && reduce4_ok(d, ep, Z)) {
-            long nb = (total / 4 + 255) / 256;
-            if (nb > 8192) nb = 8192;
-            RCOT_LAUNCH(splitk_reduce_few4_kernel, dim3((int)nb), dim3(256), 0, st, d, ep, Z);
-        } else if (d.S <= 8) {
-            long nb = (total + 255) / 256;
-            if (nb > 8192) nb = 8192;
-            RCOT_LAUNCH(splitk_reduce_few_kernel, dim3((int)nb), dim3(256), 0, st, d, ep, Z);
-        } else {
-            long nb = (total + 63) / 64;
-            if (nb > 8192) nb = 8192;
-            RCOT_LAUNCH(splitk_reduce_kernel, dim3((int)nb), dim3(256), 0, st, d, ep, Z);
-        }
+        launch_splitk_reduce(d, ep, Z, st);
         RCOT_LAUNCH_CHECK();
     }
     return RCOT_OK;

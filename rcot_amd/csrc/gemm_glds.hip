@@ -648,19 +648,9 @@ int launch_xx(XXP p, bool ln, int Z, hipStream_t st) {
     const int nk = cdiv(p.K, BK);
     const size_t smem = sizeof(float) * ((size_t)xx_nst<BM, BN>() * BK * (AW + BN) + (ln ? 2 * (size_t)nk * BK : 0));
     dim3 grid(p.tilesM * p.tilesN, 1, Z);
-    if (ln) {
-        static bool once = (hipFuncSetAttribute((const void*)gemm_xx_kernel<BM, BN, WM, WN, true>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess);
-        (void)once;
-        note_kernel("gemm_xx_kernel<%d, %d, %d, %d, true>", BM, BN, WM, WN);
-        RCOT_LAUNCH((gemm_xx_kernel<BM, BN, WM, WN, true>), grid, dim3(GEMM_NT), smem, st, p);
-    } else {
-        static bool once = (hipFuncSetAttribute((const void*)gemm_xx_kernel<BM, BN, WM, WN, false>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess);
-        (void)once;
-        note_kernel("gemm_xx_kernel<%d, %d, %d, %d, false>", BM, BN, WM, WN);
-        RCOT_LAUNCH((gemm_xx_kernel<BM, BN, WM, WN, false>), grid, dim3(GEMM_NT), smem, st, p);
-    }
+    note_kernel("gemm_xx_kernel<%d, %d, %d, %d, %s>", BM, BN, WM, WN, tf(ln));
+    if (ln) launch_lds<gemm_xx_kernel<BM, BN, WM, WN, true>>(grid, dim3(GEMM_NT), smem, st, p);
+    else launch_lds<gemm_xx_kernel<BM, BN, WM, WN, false>>(grid, dim3(GEMM_NT), smem, st, p);
     RCOT_LAUNCH_CHECK();
     return RCOT_OK;
 }
@@ -669,6 +659,53 @@ inline EpiP p_ep_probe(float* C, long ldc, long sCo, long sCi, const float* R, l
     EpiP e{};
     e.C = C; e.ldc = ldc; e.sCo = sCo; e.sCi = sCi; e.R = R; e.ldr = ldr; e.sRo = sRo; e.sRi = sRi;
     return e;
+}
+
+// The argument checks every entry point of the family makes on one product, and its parameter block: operands, output, residual and
+// rowscale of `q`, alpha = 1, beta = 0, no LayerNorm.  An entry point's own conditions and fields stay with it.
+int xx_fill(const rcot_kmajor_desc& q, int N, XXP& p) {
+    if (!q.At || !q.Bm || !q.C || q.Zo <= 0 || q.Zi <= 0 || q.M <= 0 || N <= 0 || q.K <= 0) return RCOT_EINVAL;
+    if ((N % 64) || (q.lda & 3) || (q.ldb & 3) || (q.sAo & 3) || (q.sAi & 3) || (q.sBo & 3) || (q.sBi & 3) || q.lda < 4 ||
+        !al16(q.At) || !al16(q.Bm))
+        return RCOT_EINVAL;
+    if (q.a_rows < cdiv(q.K, BK) * BK) return RCOT_EINVAL;              // zero rows up to ceil16(K) must exist
+    if (!epi_vec_ok(p_ep_probe(q.C, q.ldc, q.sCo, q.sCi, q.R, q.ldr, q.sRo, q.sRi), N)) return RCOT_EINVAL;
+    if ((long)q.Zo * q.Zi > 65535) return RCOT_EINVAL;
+    p = XXP{};
+    p.M = q.M; p.N = N; p.K = q.K; p.Zi = q.Zi;
+    p.At = q.At; p.lda = q.lda; p.sAo = q.sAo; p.sAi = q.sAi;
+    p.B = q.Bm; p.ldb = q.ldb; p.sBo = q.sBo; p.sBi = q.sBi;
+    p.ep.C = q.C; p.ep.ldc = q.ldc; p.ep.sCo = q.sCo; p.ep.sCi = q.sCi;
+    p.ep.R = q.R; p.ep.ldr = q.ldr; p.ep.sRo = q.sRo; p.ep.sRi = q.sRi;
+    p.ep.rowscale = q.rowscale; p.ep.sSo = q.sSo; p.ep.sSi = q.sSi;
+    p.ep.alpha = 1.f; p.ep.beta = 0.f; p.ep.lrelu = 1.f;
+    return RCOT_OK;
+}
+
+// streaming stores when the output is larger than the L2s can hold for its consumer (and nothing is accumulated into it)
+inline int xx_nts(long out_bytes, float beta) {
+    static const long mb = getenv("RCOT_XX_NTS_MB") ? atol(getenv("RCOT_XX_NTS_MB")) : 32;     // (read once)
+    return (mb > 0 && beta == 0.f && out_bytes >= (mb << 20)) ? 1 : 0;
+}
+
+// The tile rule of the family: f(XXTile<BM, BN, WM, WN>{}) for a product of M0 rows (of a merged launch: its FIRST product), where
+// every product sharing the grid has at most mmax rows.  A new tile form is a new line here.
+template <int BM_, int BN_, int WM_, int WN_>
+struct XXTile {
+    static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_;
+};
+template <class F>
+inline int with_xx_tile(int mmax, int M0, int N, int Z, F&& f) {
+    const long pad96 = (long)cdiv(M0, 96) * 96, pad128 = (long)cdiv(M0, 128) * 128;
+    const long big_tiles = (long)cdiv(M0, 128) * (N / 128) * Z;
+    if ((N % 128) == 0 && big_tiles >= 192) {
+        // M <= 64 (the 48-channel level: 48 <- 48 / 127 / 144 / 254): a 64-row tile on 1 x 4 wavefronts — a third less MFMA work than the 96-row
+        // tile these products rode in through round 5 (half of whose rows they left empty); same bits (round 6)
+        if (mmax <= 64) return f(XXTile<64, 128, 1, 4>{});
+        if (pad96 < pad128) return f(XXTile<96, 128, 1, 4>{});
+        return f(XXTile<128, 128, 2, 2>{});
+    }
+    return f(XXTile<64, 64, 2, 2>{});   // small-N levels: 4x more workgroups
 }
 
 }  // namespace
@@ -680,29 +717,16 @@ int rcot_gemm_kmajor(const float* At, long lda, long sAo, long sAi, int a_rows, 
                      const float* rowscale, long sSo, long sSi, float* ln_mu, float* ln_rs, long sLN, int ln_compute,
                      const float* ln_w, const float* ln_b, const float* AtF, const float* ln_c12, const void* Asplit, int Zo,
                      int Zi, int M, int N, int K, float beta, float* ws, size_t ws_bytes, int prec, void* stream) {
-    if (!At || !Bm || !C || Zo <= 0 || Zi <= 0 || M <= 0 || N <= 0 || K <= 0) return RCOT_EINVAL;
-    if ((N % 64) || (lda & 3) || (ldb & 3) || (sAo & 3) || (sAi & 3) || (sBo & 3) || (sBi & 3) || lda < 4 ||
-        !al16(At) || !al16(Bm))
-        return RCOT_EINVAL;
-    if (a_rows < cdiv(K, BK) * BK) return RCOT_EINVAL;              // zero rows up to ceil16(K) must exist
-    if (!epi_vec_ok(p_ep_probe(C, ldc, sCo, sCi, R, ldr, sRo, sRi), N)) return RCOT_EINVAL;
-    if ((long)Zo * Zi > 65535) return RCOT_EINVAL;
+    XXP p;
+    const int rcf = xx_fill({At, lda, sAo, sAi, a_rows, Bm, ldb, sBo, sBi, C, ldc, sCo, sCi, R, ldr, sRo, sRi, rowscale, sSo, sSi, Zo, Zi,
+                             M, K}, N, p);
+    if (rcf != RCOT_OK) return rcf;
     const bool ln = ln_mu != nullptr;
     if (ln && (!ln_rs || !ln_w || !ln_b || K > 4096)) return RCOT_EINVAL;
-    XXP p{};
-    p.M = M; p.N = N; p.K = K; p.Zi = Zi;
-    p.At = At; p.lda = lda; p.sAo = sAo; p.sAi = sAi;
-    p.B = Bm; p.ldb = ldb; p.sBo = sBo; p.sBi = sBi;
     p.mu = ln_mu; p.rs = ln_rs; p.sLN = sLN; p.lnw = ln_w; p.lnb = ln_b;
-    p.ep.C = C; p.ep.ldc = ldc; p.ep.sCo = sCo; p.ep.sCi = sCi;
-    p.ep.R = R; p.ep.ldr = ldr; p.ep.sRo = sRo; p.ep.sRi = sRi;
-    p.ep.rowscale = rowscale; p.ep.sSo = sSo; p.ep.sSi = sSi;
-    p.ep.alpha = 1.f; p.ep.beta = beta; p.ep.lrelu = 1.f;
+    p.ep.beta = beta;
     const int Z = Zo * Zi;
-    {   // streaming stores when the output is larger than the L2s can hold for its consumer (and nothing is accumulated into it)
-        static const long mb = getenv("RCOT_XX_NTS_MB") ? atol(getenv("RCOT_XX_NTS_MB")) : 32;     // (read once)
-        p.ep.nts = (mb > 0 && beta == 0.f && 4L * M * N * Z >= (mb << 20)) ? 1 : 0;
-    }
+    p.ep.nts = xx_nts(4L * M * N * Z, beta);
     // RCOT_PREC_BF16X1: the split-bf16 kernels and packs of RCOT_PREC_BF16X3 with the hi * hi product alone (EpiP::one)
     const bool x1 = prec == RCOT_PREC_BF16X1;
     if (x1) {
@@ -751,31 +775,24 @@ int rcot_gemm_kmajor(const float* At, long lda, long sAo, long sAi, int a_rows, 
                                           (hipStream_t)stream);
         if (rc != NOT_ELIGIBLE) return rc;
     }
-    const long pad96 = (long)cdiv(M, 96) * 96, pad128 = (long)cdiv(M, 128) * 128;
-    const long big_tiles = (long)cdiv(M, 128) * (N / 128) * Z;
-    if ((N % 128) == 0 && big_tiles >= 192) {
-        // M <= 64 (the 48-channel level: 48 <- 48 / 127 / 144 / 254): a 64-row tile on 1 x 4 wavefronts — a third less MFMA work than the 96-row
-        // tile these products rode in through round 5 (half of whose rows they left empty); same bits (round 6)
-        if (M <= 64) return launch_xx<64, 128, 1, 4>(p, ln, Z, (hipStream_t)stream);
-        const bool w96 = pad96 < pad128;
-        if (w96) return launch_xx<96, 128, 1, 4>(p, ln, Z, (hipStream_t)stream);
-        return launch_xx<128, 128, 2, 2>(p, ln, Z, (hipStream_t)stream);
-    }
-    // long reductions on few workgroups (the data gradients of the 32x32 / 16x16 planes): the eight-wavefront k-group form
-    constexpr int kg_mink = 512, kg_maxwg = 512;     // measured: profiles/r05_ab_kg.txt
-    const long wgs64 = (long)cdiv(M, 64) * (N / 64) * Z;
-    if (!ln && K >= kg_mink && wgs64 <= kg_maxwg) {
-        p.tilesM = cdiv(M, 64);
-        p.tilesN = N / 64;
-        const size_t smem = sizeof(float) * (size_t)KG_NST * BK * 128;
-        static bool once = (hipFuncSetAttribute((const void*)gemm_xx_kg_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess);
-        (void)once;
-        note_kernel("gemm_xx_kg_kernel");
-        RCOT_LAUNCH(gemm_xx_kg_kernel, dim3(p.tilesM * p.tilesN, 1, Z), dim3(512), smem, (hipStream_t)stream, p);
-        RCOT_LAUNCH_CHECK();
-        return RCOT_OK;
-    }
-    return launch_xx<64, 64, 2, 2>(p, ln, Z, (hipStream_t)stream);   // small-N levels: 4x more workgroups
+    return with_xx_tile(M, M, N, Z, [&](auto t) {
+        using T = decltype(t);
+        if constexpr (T::BN == 64) {
+            // long reductions on few workgroups (the data gradients of the 32x32 / 16x16 planes): the eight-wavefront k-group form
+            constexpr int kg_mink = 512, kg_maxwg = 512;     // measured: profiles/r05_ab_kg.txt
+            const long wgs64 = (long)cdiv(M, 64) * (N / 64) * Z;
+            if (!ln && K >= kg_mink && wgs64 <= kg_maxwg) {
+                p.tilesM = cdiv(M, 64);
+                p.tilesN = N / 64;
+                const size_t smem = sizeof(float) * (size_t)KG_NST * BK * 128;
+                note_kernel("gemm_xx_kg_kernel");
+                launch_lds<gemm_xx_kg_kernel>(dim3(p.tilesM * p.tilesN, 1, Z), dim3(512), smem, (hipStream_t)stream, p);
+                RCOT_LAUNCH_CHECK();
+                return RCOT_OK;
+            }
+        }
+        return launch_xx<T::BM, T::BN, T::WM, T::WN>(p, ln, Z, (hipStream_t)stream);
+    });
 }
 
 int rcot_gemm_kmajor_stats(const float* At, long lda, long sAo, long sAi, int a_rows, const float* Bm, long ldb, long sBo, long sBi,
@@ -783,37 +800,23 @@ int rcot_gemm_kmajor_stats(const float* At, long lda, long sAo, long sAi, int a_
                            float* st_rs, long sST, int Zo, int Zi, int M, int N, int K, void* stream) {
     if (!At || !Bm || !C || !st_mu || !st_rs || Zo <= 0 || Zi != 1 || M <= 0 || N <= 0 || K <= 0) return RCOT_EINVAL;
     if (M > 96 || (N % 128)) return RCOT_EUNSUPPORTED;                // one row tile must hold every channel of its pixels
-    if ((lda & 3) || (ldb & 3) || (sAo & 3) || (sAi & 3) || (sBo & 3) || (sBi & 3) || lda < 4 || !al16(At) || !al16(Bm) || (sST & 3) ||
-        !al16(st_mu) || !al16(st_rs))
-        return RCOT_EINVAL;
-    if (a_rows < cdiv(K, BK) * BK) return RCOT_EINVAL;
-    if (!epi_vec_ok(p_ep_probe(C, ldc, sCo, sCi, R, ldr, sRo, sRi), N)) return RCOT_EINVAL;
-    if ((long)Zo > 65535) return RCOT_EINVAL;
-    XXP p{};
-    p.M = M; p.N = N; p.K = K; p.Zi = 1;
-    p.At = At; p.lda = lda; p.sAo = sAo; p.sAi = sAi;
-    p.B = Bm; p.ldb = ldb; p.sBo = sBo; p.sBi = sBi;
-    p.ep.C = C; p.ep.ldc = ldc; p.ep.sCo = sCo; p.ep.sCi = sCi;
-    p.ep.R = R; p.ep.ldr = ldr; p.ep.sRo = sRo; p.ep.sRi = sRi;
-    p.ep.alpha = 1.f; p.ep.beta = 0.f; p.ep.lrelu = 1.f;
+    if ((sST & 3) || !al16(st_mu) || !al16(st_rs)) return RCOT_EINVAL;
+    XXP p;
+    const int rcf = xx_fill({At, lda, sAo, sAi, a_rows, Bm, ldb, sBo, sBi, C, ldc, sCo, sCi, R, ldr, sRo, sRi, nullptr, 0, 0, Zo, 1, M, K},
+                            N, p);
+    if (rcf != RCOT_OK) return rcf;
     p.st_mu = st_mu; p.st_rs = st_rs; p.sST = sST;
-    static const long mb = getenv("RCOT_XX_NTS_MB") ? atol(getenv("RCOT_XX_NTS_MB")) : 32;
-    p.ep.nts = (mb > 0 && 4L * M * N * Zo >= (mb << 20)) ? 1 : 0;
+    p.ep.nts = xx_nts(4L * M * N * Zo, 0.f);
     p.tilesM = 1;
     p.tilesN = N / 128;
     hipStream_t st = (hipStream_t)stream;
+    note_kernel("gemm_xx_stats_kernel<%d>", M <= 64 ? 64 : 96);
     if (M <= 64) {
         const size_t smem = sizeof(float) * (size_t)XX_NST * BK * (64 + 128);
-        static bool once = (hipFuncSetAttribute((const void*)gemm_xx_stats_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess);
-        (void)once;
-        note_kernel("gemm_xx_stats_kernel<64>");
-        RCOT_LAUNCH(gemm_xx_stats_kernel<64>, dim3(p.tilesN, 1, Zo), dim3(GEMM_NT), smem, st, p);
+        launch_lds<gemm_xx_stats_kernel<64>>(dim3(p.tilesN, 1, Zo), dim3(GEMM_NT), smem, st, p);
     } else {
         const size_t smem = sizeof(float) * (size_t)XX_NST * BK * (128 + 128);
-        static bool once = (hipFuncSetAttribute((const void*)gemm_xx_stats_kernel<96>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess);
-        (void)once;
-        note_kernel("gemm_xx_stats_kernel<96>");
-        RCOT_LAUNCH(gemm_xx_stats_kernel<96>, dim3(p.tilesN, 1, Zo), dim3(GEMM_NT), smem, st, p);
+        launch_lds<gemm_xx_stats_kernel<96>>(dim3(p.tilesN, 1, Zo), dim3(GEMM_NT), smem, st, p);
     }
     RCOT_LAUNCH_CHECK();
     return RCOT_OK;
@@ -825,68 +828,34 @@ int rcot_gemm_kmajor_multi(const rcot_kmajor_desc* d, int n, int N, int prec, vo
     if (!d || n < 1 || n > 3 || N <= 0) return RCOT_EINVAL;
     // the split-bf16 arithmetic runs these products on gemm_x3_kernel (one launch each): not merged
     if (prec != RCOT_PREC_FP32 && prec != RCOT_PREC_BF16X6) return RCOT_EUNSUPPORTED;
-    if (N % 64) return RCOT_EINVAL;
     XXP3 P{};
+    int nz[3], mmax = 0;
     for (int i = 0; i < 3; ++i) {
-        const rcot_kmajor_desc& q = d[i < n ? i : 0];
-        if (!q.At || !q.Bm || !q.C || q.Zo <= 0 || q.Zi <= 0 || q.M <= 0 || q.K <= 0) return RCOT_EINVAL;
-        if ((q.lda & 3) || (q.ldb & 3) || (q.sAo & 3) || (q.sAi & 3) || (q.sBo & 3) || (q.sBi & 3) || q.lda < 4 || !al16(q.At) ||
-            !al16(q.Bm))
-            return RCOT_EINVAL;
-        if (q.a_rows < cdiv(q.K, BK) * BK) return RCOT_EINVAL;
-        if (!epi_vec_ok(p_ep_probe(q.C, q.ldc, q.sCo, q.sCi, q.R, q.ldr, q.sRo, q.sRi), N)) return RCOT_EINVAL;
-        if ((long)q.Zo * q.Zi > 65535) return RCOT_EINVAL;
-        XXP& p = P.q[i];
-        p.M = q.M; p.N = N; p.K = q.K; p.Zi = q.Zi;
-        p.At = q.At; p.lda = q.lda; p.sAo = q.sAo; p.sAi = q.sAi;
-        p.B = q.Bm; p.ldb = q.ldb; p.sBo = q.sBo; p.sBi = q.sBi;
-        p.ep.C = q.C; p.ep.ldc = q.ldc; p.ep.sCo = q.sCo; p.ep.sCi = q.sCi;
-        p.ep.R = q.R; p.ep.ldr = q.ldr; p.ep.sRo = q.sRo; p.ep.sRi = q.sRi;
-        p.ep.rowscale = q.rowscale; p.ep.sSo = q.sSo; p.ep.sSi = q.sSi;
-        p.ep.alpha = 1.f; p.ep.beta = 0.f; p.ep.lrelu = 1.f;
+        const int rcf = xx_fill(d[i < n ? i : 0], N, P.q[i]);
+        if (rcf != RCOT_OK) return rcf;
+        nz[i] = i < n ? d[i].Zo * d[i].Zi : 0;
+        mmax = P.q[i].M > mmax ? P.q[i].M : mmax;
     }
-    int nz[3];
-    for (int i = 0; i < 3; ++i) nz[i] = i < n ? d[i].Zo * d[i].Zi : 0;
-    // one tile shape for the grid, chosen as rcot_gemm_kmajor chooses for the FIRST product (the full-channel one: dV); the per-element
-    // summation order does not depend on the tile, so every product equals its own single launch bit for bit
-    int total = 0;
-    auto plan = [&](int BM, int BN) {
-        total = 0;
+    // one tile shape for the grid, chosen by the rule of rcot_gemm_kmajor for the FIRST product (the full-channel one: dV), never its
+    // k-group kernel; the per-element summation order does not depend on the tile, so every product equals its own single launch bit
+    // for bit
+    return with_xx_tile(mmax, P.q[0].M, N, nz[0], [&](auto t) {
+        using T = decltype(t);
+        int total = 0;
         for (int i = 0; i < 3; ++i) {
-            P.q[i].tilesM = cdiv(P.q[i].M, BM);
-            P.q[i].tilesN = N / BN;
+            P.q[i].tilesM = cdiv(P.q[i].M, T::BM);
+            P.q[i].tilesN = N / T::BN;
             P.first[i] = total;
             total += P.q[i].tilesM * P.q[i].tilesN * nz[i];
         }
         P.first[3] = total;
-    };
-    const int M0 = P.q[0].M;
-    const long pad96 = (long)cdiv(M0, 96) * 96, pad128 = (long)cdiv(M0, 128) * 128;
-    const long big_tiles = (long)cdiv(M0, 128) * (N / 128) * nz[0];
-    hipStream_t st = (hipStream_t)stream;
-#define RCOT_XX_MULTI(BM, BN, WM, WN)                                                                                        \
-    do {                                                                                                                     \
-        plan(BM, BN);                                                                                                        \
-        constexpr int AW = BM <= 64 ? 64 : 128;                                                                              \
-        const size_t smem = sizeof(float) * ((size_t)xx_nst<BM, BN>() * BK * (AW + BN));                                     \
-        static bool once = (hipFuncSetAttribute((const void*)gemm_xx_multi_kernel<BM, BN, WM, WN>,                           \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess);      \
-        (void)once;                                                                                                          \
-        note_kernel("gemm_xx_multi_kernel<%d, %d, %d, %d>", BM, BN, WM, WN);                                                 \
-        RCOT_LAUNCH((gemm_xx_multi_kernel<BM, BN, WM, WN>), dim3(total), dim3(GEMM_NT), smem, st, P);                 \
-    } while (0)
-    if ((N % 128) == 0 && big_tiles >= 192) {
-        int mmax = 0;
-        for (int i = 0; i < n; ++i) mmax = P.q[i].M > mmax ? P.q[i].M : mmax;
-        if (mmax <= 64) RCOT_XX_MULTI(64, 128, 1, 4);
-        else if (pad96 < pad128) RCOT_XX_MULTI(96, 128, 1, 4);
-        else RCOT_XX_MULTI(128, 128, 2, 2);
-    } else {
-        RCOT_XX_MULTI(64, 64, 2, 2);
-    }
-#undef RCOT_XX_MULTI
-    RCOT_LAUNCH_CHECK();
-    return RCOT_OK;
+        constexpr int AW = T::BM <= 64 ? 64 : 128;
+        const size_t smem = sizeof(float) * ((size_t)xx_nst<T::BM, T::BN>() * BK * (AW + T::BN));
+        note_kernel("gemm_xx_multi_kernel<%d, %d, %d, %d>", T::BM, T::BN, T::WM, T::WN);
+        launch_lds<gemm_xx_multi_kernel<T::BM, T::BN, T::WM, T::WN>>(dim3(total), dim3(GEMM_NT), smem, (hipStream_t)stream, P);
+        RCOT_LAUNCH_CHECK();
+        return RCOT_OK;
+    });
 }
 
 int rcot_pack_weight(const float* W, long ldw, int Co, int Ci, float* WT, float* WP, const float* ln_w, const float* ln_b,

@@ -519,6 +519,26 @@ __device__ __forceinline__ void nt_body(const NTP& p, const int bx, const int bz
                          n0 + wn * TN * 32, p.M, p.ldws, lane);
 }
 
+// The tile forms of the family, cfg 0..5: TM x TN accumulator tiles of 32 x 32 per wavefront on WM x WN wavefronts; COOP is the
+// cooperative form the split arithmetics have for this tile (gemm_nt_kernel's COOP: which operand the four wavefronts share), 0 = none.
+// Every host path from a run-time cfg to a kernel goes through with_nt_tile: a new tile form is a new row here.
+template <int TM_, int TN_, int WM_, int WN_, int COOP_>
+struct NTTile {
+    static constexpr int TM = TM_, TN = TN_, WM = WM_, WN = WN_, COOP = COOP_, BM = 32 * TM_ * WM_, BN = 32 * TN_ * WN_;
+};
+constexpr int NT_CFGS = 6;
+template <class F>
+inline int with_nt_tile(int cfg, F&& f) {
+    switch (cfg) {
+        case 1: return f(NTTile<1, 3, 4, 1, 1>{});     // 128 x 96
+        case 2: return f(NTTile<3, 1, 1, 4, 2>{});     //  96 x 128
+        case 3: return f(NTTile<1, 2, 4, 1, 1>{});     // 128 x 64
+        case 4: return f(NTTile<2, 1, 1, 4, 2>{});     //  64 x 128
+        case 5: return f(NTTile<1, 1, 2, 2, 0>{});     //  64 x 64
+        default: return f(NTTile<2, 2, 2, 2, 0>{});    // 128 x 128 (cfg 0)
+    }
+}
+
 }  // namespace rcot_nt
 
 namespace rcot {

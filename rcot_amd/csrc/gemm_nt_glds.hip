@@ -96,30 +96,16 @@ int launch_nt(NTP p, const EpiP& ep, int Z, hipStream_t st, bool reduce) {
     // (the name rocprofv3 and the library's own per-launch profile list: bench.py matches its rows by it)
     if (X6) note_kernel("gemm_nt_kernel<%d, %d, %d, %d, %s, true, true, %d>", TM, TN, WM, WN, tf(p.mu != nullptr), COOP);
     else note_kernel("gemm_nt_kernel<%d, %d, %d, %d, %s, %s, false, %d>", TM, TN, WM, WN, tf(p.mu != nullptr), tf(X3), COOP);
-    if (p.mu) {
-        static bool once = (hipFuncSetAttribute((const void*)gemm_nt_kernel<TM, TN, WM, WN, true, X3, X6, COOP>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess);
-        (void)once;
-        RCOT_LAUNCH((gemm_nt_kernel<TM, TN, WM, WN, true, X3, X6, COOP>), grid, dim3(GEMM_NT), smem, st, p);
-    } else {
-        static bool once = (hipFuncSetAttribute((const void*)gemm_nt_kernel<TM, TN, WM, WN, false, X3, X6, COOP>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess);
-        (void)once;
-        RCOT_LAUNCH((gemm_nt_kernel<TM, TN, WM, WN, false, X3, X6, COOP>), grid, dim3(GEMM_NT), smem, st, p);
-    }
+    if (p.mu) launch_lds<gemm_nt_kernel<TM, TN, WM, WN, true, X3, X6, COOP>>(grid, dim3(GEMM_NT), smem, st, p);
+    else launch_lds<gemm_nt_kernel<TM, TN, WM, WN, false, X3, X6, COOP>>(grid, dim3(GEMM_NT), smem, st, p);
     RCOT_LAUNCH_CHECK();
     if (!reduce) return RCOT_OK;
     const long total = (long)p.M * p.N * Z;
-    if (p.S <= 8) {                                           // few slabs: one output per THREAD (the wave-per-slab-quarter form
-        long nb = (total + 255) / 256;                        // leaves 3 of 4 wavefronts idle and needs 4x the workgroups)
-        if (nb > 4096) nb = 4096;
-        RCOT_LAUNCH(nt_reduce_few_kernel, dim3((int)nb), dim3(256), 0, st, p.ws, p.ldws, p.S, p.M, p.N, Z, p.Zi, ep);
-        RCOT_LAUNCH_CHECK();
-        return RCOT_OK;
-    }
-    long nb = (total + 63) / 64;
-    if (nb > 8192) nb = 8192;
-    RCOT_LAUNCH(nt_reduce_kernel, dim3((int)nb), dim3(256), 0, st, p.ws, p.ldws, p.S, p.M, p.N, Z, p.Zi, ep);
+    // few slabs: one output per THREAD (the wave-per-slab-quarter form leaves 3 of 4 wavefronts idle and needs 4x the workgroups)
+    if (p.S <= 8)
+        RCOT_LAUNCH(nt_reduce_few_kernel, dim3(grid_for(total, 256, 4096)), dim3(256), 0, st, p.ws, p.ldws, p.S, p.M, p.N, Z, p.Zi, ep);
+    else
+        RCOT_LAUNCH(nt_reduce_kernel, dim3(grid_for(total, 64, 8192)), dim3(256), 0, st, p.ws, p.ldws, p.S, p.M, p.N, Z, p.Zi, ep);
     RCOT_LAUNCH_CHECK();
     return RCOT_OK;
 }
@@ -154,16 +140,17 @@ int nt_configure(int M, int N, int K, int Zo, int Zi, const float* A, long lda, 
     p.ldws = (N + 3) & ~3;
     // tile shape: least padded area among 128x128, 128x96, 96x128
     // workgroup tile: the (bm, bn) of {128, 96, 64} x {128, 96, 64} (not 96 x 96, 96 x 64, 64 x 96) with the least padded area
-    static const int cand_bm[6] = {128, 128, 96, 128, 64, 64}, cand_bn[6] = {128, 96, 128, 64, 128, 64};
-    int cfg = 0;
+    int cfg = 0, bm = 0, bn = 0;
     long best = -1;
-    for (int c = 0; c < 6; ++c) {
-        const long area = (long)cdiv(M, cand_bm[c]) * cand_bm[c] * cdiv(N, cand_bn[c]) * cand_bn[c];
-        if (best < 0 || area < best) { best = area; cfg = c; }
-    }
+    for (int c = 0; c < NT_CFGS; ++c)
+        with_nt_tile(c, [&](auto t) {
+            using T = decltype(t);
+            const long area = (long)cdiv(M, T::BM) * T::BM * cdiv(N, T::BN) * T::BN;
+            if (best < 0 || area < best) { best = area; cfg = c; bm = T::BM; bn = T::BN; }
+            return 0;
+        });
     // (forcing 64 x 64 tiles with a quarter of the split factor on the short reductions of the 16x16 / 32x32 levels measured slower,
     // 20 / 45 / 26 us against 15 / 24 / 18 us, round 3: not adopted)
-    const int bm = cand_bm[cfg], bn = cand_bn[cfg];
     const long tiles = (long)cdiv(M, bm) * cdiv(N, bn) * Z;
     const int nslab = K / BK;
     // split factor from a two-term cost model: MFMA time at the parallel efficiency the grid reaches, plus
@@ -183,9 +170,8 @@ int nt_configure(int M, int N, int K, int Zo, int Zi, const float* A, long lda, 
     if ((long)Z * S > 65535) S = 65535 / Z;
     p.kchunk = cdiv(cdiv(nslab, (int)S), 1) * BK;
     p.S = cdiv(K, p.kchunk);
-    constexpr int bms[6] = {128, 128, 96, 128, 64, 64}, bns[6] = {128, 96, 128, 64, 128, 64};
-    p.tilesM = cdiv(p.M, bms[cfg]);
-    p.tilesN = cdiv(p.N, bns[cfg]);
+    p.tilesM = cdiv(p.M, bm);
+    p.tilesN = cdiv(p.N, bn);
     *out = p;
     *out_cfg = cfg;
     return RCOT_OK;
@@ -216,40 +202,18 @@ int try_gemm_nt_glds(int M, int N, int K, int Zo, int Zi, const float* A, long l
     // (an exact-fp32 form — LayerNorm of the shared operand once per workgroup, in place, and a slab loop unrolled over the ring stages with
     // immediate offsets: 97 -> 34 VALU instructions per slab — was built and measured: 175.0 / 117.1 / 46.8 us -> 171.6 / 120.7 / 49.0, the
     // iteration 80.7 vs 80.5 ms: nothing, removed; profiles/r05_ab_coop_fp32.txt, NOTES round 5 item 20)
-    if (prec == RCOT_PREC_BF16X6 && (coop & 1) && cfg >= 1 && cfg <= 4) {
-        if (cfg == 1) return launch_nt<1, 3, 4, 1, true, true, 1>(p, ep, Z, st, reduce);
-        if (cfg == 2) return launch_nt<3, 1, 1, 4, true, true, 2>(p, ep, Z, st, reduce);
-        if (cfg == 3) return launch_nt<1, 2, 4, 1, true, true, 1>(p, ep, Z, st, reduce);
-        return launch_nt<2, 1, 1, 4, true, true, 2>(p, ep, Z, st, reduce);
-    }
-    if (prec && prec != RCOT_PREC_BF16X6 && (coop & 2) && cfg >= 1 && cfg <= 4) {
-        if (cfg == 1) return launch_nt<1, 3, 4, 1, true, false, 1>(p, ep, Z, st, reduce);
-        if (cfg == 2) return launch_nt<3, 1, 1, 4, true, false, 2>(p, ep, Z, st, reduce);
-        if (cfg == 3) return launch_nt<1, 2, 4, 1, true, false, 1>(p, ep, Z, st, reduce);
-        return launch_nt<2, 1, 1, 4, true, false, 2>(p, ep, Z, st, reduce);
-    }
-    if (prec == RCOT_PREC_BF16X6) {
-        if (cfg == 1) return launch_nt<1, 3, 4, 1, true, true>(p, ep, Z, st, reduce);
-        if (cfg == 2) return launch_nt<3, 1, 1, 4, true, true>(p, ep, Z, st, reduce);
-        if (cfg == 3) return launch_nt<1, 2, 4, 1, true, true>(p, ep, Z, st, reduce);
-        if (cfg == 4) return launch_nt<2, 1, 1, 4, true, true>(p, ep, Z, st, reduce);
-        if (cfg == 5) return launch_nt<1, 1, 2, 2, true, true>(p, ep, Z, st, reduce);
-        return launch_nt<2, 2, 2, 2, true, true>(p, ep, Z, st, reduce);
-    }
-    if (prec) {
-        if (cfg == 1) return launch_nt<1, 3, 4, 1, true>(p, ep, Z, st, reduce);
-        if (cfg == 2) return launch_nt<3, 1, 1, 4, true>(p, ep, Z, st, reduce);
-        if (cfg == 3) return launch_nt<1, 2, 4, 1, true>(p, ep, Z, st, reduce);
-        if (cfg == 4) return launch_nt<2, 1, 1, 4, true>(p, ep, Z, st, reduce);
-        if (cfg == 5) return launch_nt<1, 1, 2, 2, true>(p, ep, Z, st, reduce);
-        return launch_nt<2, 2, 2, 2, true>(p, ep, Z, st, reduce);
-    }
-    if (cfg == 1) return launch_nt<1, 3, 4, 1, false>(p, ep, Z, st, reduce);
-    if (cfg == 2) return launch_nt<3, 1, 1, 4, false>(p, ep, Z, st, reduce);
-    if (cfg == 3) return launch_nt<1, 2, 4, 1, false>(p, ep, Z, st, reduce);
-    if (cfg == 4) return launch_nt<2, 1, 1, 4, false>(p, ep, Z, st, reduce);
-    if (cfg == 5) return launch_nt<1, 1, 2, 2, false>(p, ep, Z, st, reduce);
-    return launch_nt<2, 2, 2, 2, false>(p, ep, Z, st, reduce);
+    const bool x6 = prec == RCOT_PREC_BF16X6, x3 = prec && !x6;
+    const bool split_once = x6 ? (coop & 1) : (x3 && (coop & 2));
+    return with_nt_tile(cfg, [&](auto t) {
+        using T = decltype(t);
+        if constexpr (T::COOP != 0) {
+            if (split_once && x6) return launch_nt<T::TM, T::TN, T::WM, T::WN, true, true, T::COOP>(p, ep, Z, st, reduce);
+            if (split_once) return launch_nt<T::TM, T::TN, T::WM, T::WN, true, false, T::COOP>(p, ep, Z, st, reduce);
+        }
+        if (x6) return launch_nt<T::TM, T::TN, T::WM, T::WN, true, true>(p, ep, Z, st, reduce);
+        if (x3) return launch_nt<T::TM, T::TN, T::WM, T::WN, true>(p, ep, Z, st, reduce);
+        return launch_nt<T::TM, T::TN, T::WM, T::WN, false>(p, ep, Z, st, reduce);
+    });
 }
 
 }  // namespace rcot

@@ -31,16 +31,15 @@ EpiP epi_default(float* C, long ldc) {
 // A strided (weights), B x-contiguous (activations, pixels along N).
 int run_strided_xcontig(bool a_kfast, GemmDims d, const StridedP& ap, const XContigP& bp, const EpiP& ep, int Z,
                         hipStream_t st) {
-    LaunchPlan pl = plan_gemm(d.M, d.N, d.K, Z, false, 0);
-    d.S = 1; d.kchunk = cdiv(d.K, BK) * BK; d.ws = nullptr;
+    const bool big = plan_splitk(d, Z, nullptr, 0);
     // 96-row tile (1x4 wavefronts, each 96x32): M = 96/192/288/576 (C, 3C of the 96- and 192-channel levels)
     // fill it exactly, where the 128-row tile would idle a quarter of its MFMAs.
     const long pad96 = (long)cdiv(d.M, 96) * 96, pad128 = (long)cdiv(d.M, 128) * 128;
     // (k-fast A operands only: the x-fast element map of StridedLoader needs GEMM_NT % rows == 0, which 96 rows violate —
     // the unpacked data gradient of a 96-channel level at B*N >= 384 tiles used to come out wrong on this tile)
-    if (pl.big && pad96 < pad128 && a_kfast)
+    if (big && pad96 < pad128 && a_kfast)
         return launch_gemm_cfg<CfgM, AStrK<CfgM>, StridedP, BXc<CfgM>, XContigP>(d, ap, bp, ep, Z, st);
-    if (pl.big) {
+    if (big) {
         if (a_kfast) return launch_gemm_cfg<CfgL, AStrK<CfgL>, StridedP, BXc<CfgL>, XContigP>(d, ap, bp, ep, Z, st);
         return launch_gemm_cfg<CfgL, AStrM<CfgL>, StridedP, BXc<CfgL>, XContigP>(d, ap, bp, ep, Z, st);
     }
@@ -51,24 +50,16 @@ int run_strided_xcontig(bool a_kfast, GemmDims d, const StridedP& ap, const XCon
 // Both operands k-contiguous (reduction over pixels), split-K slabs.
 int run_kcontig(GemmDims d, const KContigP& ap, const KContigP& bp, const EpiP& ep, int Z, float* ws,
                 size_t ws_bytes, hipStream_t st) {
-    LaunchPlan pl = plan_gemm(d.M, d.N, d.K, Z, true, ws ? ws_bytes : 0);
-    d.S = pl.S;
-    d.kchunk = cdiv(cdiv(d.K, d.S), BK) * BK;
-    d.S = cdiv(d.K, d.kchunk);
-    d.ws = ws;
+    const bool big = plan_splitk(d, Z, ws, ws_bytes);
     if (d.S > 1 && (size_t)d.M * d.N * Z * d.S * sizeof(float) > ws_bytes) return RCOT_EWORKSPACE;
-    if (pl.big) return launch_gemm_cfg<CfgL, AKc<CfgL>, KContigP, BKc<CfgL>, KContigP>(d, ap, bp, ep, Z, st);
+    if (big) return launch_gemm_cfg<CfgL, AKc<CfgL>, KContigP, BKc<CfgL>, KContigP>(d, ap, bp, ep, Z, st);
     return launch_gemm_cfg<CfgS, AKc<CfgS>, KContigP, BKc<CfgS>, KContigP>(d, ap, bp, ep, Z, st);
 }
 
 // Both operands scalar-strided (Linear layers: tiny batch, weight-bandwidth bound), split-K.
 int run_strided2(bool a_kfast, GemmDims d, const StridedP& ap, const StridedP& bp, const EpiP& ep, float* ws,
                  size_t ws_bytes, hipStream_t st) {
-    LaunchPlan pl = plan_gemm(d.M, d.N, d.K, 1, ws != nullptr, ws_bytes);
-    d.S = pl.S;
-    d.kchunk = cdiv(cdiv(d.K, d.S), BK) * BK;
-    d.S = cdiv(d.K, d.kchunk);
-    d.ws = ws;
+    plan_splitk(d, 1, ws, ws_bytes);
     if (a_kfast) return launch_gemm_cfg<CfgS, AStrK<CfgS>, StridedP, BStrK<CfgS>, StridedP, true>(d, ap, bp, ep, 1, st);
     return launch_gemm_cfg<CfgS, AStrM<CfgS>, StridedP, BStrK<CfgS>, StridedP, true>(d, ap, bp, ep, 1, st);
 }
@@ -248,7 +239,7 @@ int rcot_linear_wgrad(const float* dY, const float* X, float* dW, int B, int in,
         return run_strided_xcontig(false, d, ap, bp, ep, 1, (hipStream_t)stream);
     }
     StridedP bp{X, 1, (long)in, 0, 0, in, B};        // B(k=b,n=i) = X[b*in + i]
-    d.S = 1; d.kchunk = cdiv(d.K, BK) * BK; d.ws = nullptr;
+    plan_splitk(d, 1, nullptr, 0);
     // n-contiguous B through the scalar k-fast loader would be uncoalesced; this path is only the unaligned fallback
     return launch_gemm_cfg<CfgS, AStrM<CfgS>, StridedP, BStrK<CfgS>, StridedP, true>(d, ap, bp, ep, 1, (hipStream_t)stream);
 }

@@ -372,11 +372,8 @@ template <int TM, int WM, int WN, bool LNP, int NST>
 int launch_x3_k(const X3P& p, int grid, hipStream_t st) {
     constexpr int BM = 32 * TM * WM, BN = 128 * WN, AW = BM <= 64 ? 64 : 128;
     const size_t smem = sizeof(float) * ((size_t)NST * BK * (AW + BN) + 256);
-    static bool once = (hipFuncSetAttribute((const void*)gemm_x3_kernel<TM, WM, WN, LNP, NST>,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess);
-    (void)once;
     note_kernel("gemm_x3_kernel<%d, %d, %d, %s, %d>", TM, WM, WN, tf(LNP), NST);
-    RCOT_LAUNCH((gemm_x3_kernel<TM, WM, WN, LNP, NST>), dim3(grid), dim3(64 * WM * WN), smem, st, p);
+    launch_lds<gemm_x3_kernel<TM, WM, WN, LNP, NST>>(dim3(grid), dim3(64 * WM * WN), smem, st, p);
     RCOT_LAUNCH_CHECK();
     return RCOT_OK;
 }
@@ -398,36 +395,20 @@ int launch_x3(X3P p, bool ln, int Z, hipStream_t st, size_t ws_bytes) {
     // split-K when the output tiles alone cannot fill the chip and the reduction is long
     const int nk = cdiv(p.K, BK);
     const int base = p.tilesM * p.tilesN * Z;
-    int S = 1;
-    if (p.ws && base < 256 && nk >= 16) {
-        // two workgroups per CU: a lone wavefront per SIMD runs its slab chain (LDS reads -> split -> MFMA -> barrier) at
-        // ~0.8 us per slab whatever the ring depth, a second workgroup fills those gaps (measured: 512 pieces beat 256
-        // despite the extra slab traffic: 31.6 vs 36.7 us on C=384 <- 2042 at 16x16)
-        S = cdiv(512, base);
-        if (S > nk / 8) S = nk / 8;                                   // >= 8 slabs per piece
-        while (S > 1 && (size_t)S * Z * p.M * p.N * sizeof(float) > ws_bytes) --S;
-        if (S < 1) S = 1;
-    }
-    p.kchunk = cdiv(nk, S);
-    p.S = cdiv(nk, p.kchunk);
-    if (p.S > 1 && nk - (p.S - 1) * p.kchunk < 2) {                   // the slab ring needs two slabs in every piece
-        p.kchunk = cdiv(nk, p.S - 1);
-        p.S = cdiv(nk, p.kchunk);
-    }
-    p.ntiles = base * p.S;
-    // every workgroup gets the same number of tiles (+-1): grid = tiles / rounds
-    const int rounds = cdiv(p.ntiles, PER_CU * 256);
-    const int grid = cdiv(p.ntiles, rounds);
+    // two workgroups per CU: a lone wavefront per SIMD runs its slab chain (LDS reads -> split -> MFMA -> barrier) at
+    // ~0.8 us per slab whatever the ring depth, a second workgroup fills those gaps (measured: 512 pieces beat 256
+    // despite the extra slab traffic: 31.6 vs 36.7 us on C=384 <- 2042 at 16x16)
+    const int want = (p.ws && base < 256 && nk >= 16) ? cdiv(512, base) : 1;
+    const SlabCut cut = cut_slabs(nk, base, want, (size_t)Z * p.M * p.N * sizeof(float), ws_bytes);
+    p.S = cut.S; p.kchunk = cut.kchunk; p.ntiles = cut.ntiles;
+    const int grid = cut.grid(PER_CU * 256);
     int rc;
     const bool deep = grid <= 256;
     if (ln) rc = deep ? launch_x3_k<TM, WM, WN, true, NST_DEEP>(p, grid, st) : launch_x3_k<TM, WM, WN, true, NST_STREAM>(p, grid, st);
     else rc = deep ? launch_x3_k<TM, WM, WN, false, NST_DEEP>(p, grid, st) : launch_x3_k<TM, WM, WN, false, NST_STREAM>(p, grid, st);
     if (rc != RCOT_OK) return rc;
     if (p.S > 1) {
-        const long per = (long)p.M * (p.N / 4);
-        long nb = (per + 255) / 256;
-        if (nb > 2048) nb = 2048;
-        RCOT_LAUNCH(x3_reduce_kernel, dim3((int)nb, Z), dim3(256), 0, st, p.ws, p.S, p.M, p.N / 4, p.Zi, p.ep);
+        RCOT_LAUNCH(x3_reduce_kernel, dim3(slab_reduce_grid(p.M, p.N), Z), dim3(256), 0, st, p.ws, p.S, p.M, p.N / 4, p.Zi, p.ep);
         RCOT_LAUNCH_CHECK();
     }
     return RCOT_OK;

@@ -620,36 +620,21 @@ int configure_p(P& p, bool ln, int Z, size_t ws_bytes, bool stat, int* grid_out,
     p.tilesN = p.N / (128 * WN);
     const int nk = cdiv(p.K, BK);
     const int base = p.tilesM * p.tilesN * Z;
-    int S = 1;
     constexpr int nk_min = 16;                                          // split only reductions of >= nk_min slabs
     // split when the tiles fill less than a third of the chip: at half (128 of 256 slots: the 64x64 level with one row tile) two
     // K pieces + the reduce launch measured 25.4 / 26.9 / 30.9 us against 20.0 / 25.6 / 30.3 us unsplit (K = 288 / 255 / 510)
-    if (p.ws && base * 3 <= slots && nk >= nk_min) {
-        S = slots / base;
-        if (S > nk / 8) S = nk / 8;
-        while (S > 1 && (size_t)S * Z * p.M * p.N * sizeof(float) > ws_bytes) --S;
-        if (S < 1) S = 1;
-    }
-    p.kchunk = cdiv(nk, S);
-    p.S = cdiv(nk, p.kchunk);
-    if (p.S > 1 && nk - (p.S - 1) * p.kchunk < 2) {
-        p.kchunk = cdiv(nk, p.S - 1);
-        p.S = cdiv(nk, p.kchunk);
-    }
+    const int want = (p.ws && base * 3 <= slots && nk >= nk_min) ? slots / base : 1;
+    const SlabCut cut = cut_slabs(nk, base, want, (size_t)Z * p.M * p.N * sizeof(float), ws_bytes);
+    p.S = cut.S; p.kchunk = cut.kchunk; p.ntiles = cut.ntiles;
     if (stat && (p.S > 1 || !ln || (p.K % BK))) return RCOT_EUNSUPPORTED;   // a K piece does not see the whole column
-    p.ntiles = base * p.S;
-    const int rounds = cdiv(p.ntiles, slots);
-    *grid_out = cdiv(p.ntiles, rounds);
+    *grid_out = cut.grid(slots);
     *smem_out = (size_t)(D + 1) * 4096 * NT + (size_t)D * 8192 * WN + (size_t)2 * 4096 * NT * WN +
                 (stat ? 2 * 2 * 128 * WN * sizeof(float) : 0);
     return RCOT_OK;
 }
 
 inline void launch_p_reduce(const P& p, int Z, hipStream_t st) {
-    const long per = (long)p.M * (p.N / 4);
-    long nb = (per + 255) / 256;
-    if (nb > 2048) nb = 2048;
-    RCOT_LAUNCH(x3w_reduce_kernel, dim3((int)nb, Z), dim3(256), 0, st, p.ws, p.S, p.M, p.N / 4, p.Zi, p.ep);
+    RCOT_LAUNCH(x3w_reduce_kernel, dim3(slab_reduce_grid(p.M, p.N), Z), dim3(256), 0, st, p.ws, p.S, p.M, p.N / 4, p.Zi, p.ep);
 }
 
 template <int WN, int D, int NT = 2>
@@ -659,21 +644,15 @@ int launch_p(P p, bool ln, int Z, hipStream_t st, size_t ws_bytes, bool stat = f
     const int rcc = configure_p<WN, D, NT>(p, ln, Z, ws_bytes, stat, &grid, &smem);
     if (rcc != RCOT_OK) return rcc;
     const bool add = p.S == 1 && (p.ep.R != nullptr || p.ep.beta != 0.f);
-#define X3P_LAUNCH(L, A, T)                                                                                                       \
-    do {                                                                                                                           \
-        note_kernel("x3p_kernel<%s, %s, %d, %d, false, %s, %d>", tf(L), tf(A), WN, D, tf(T), NT);                                  \
-        static bool once = (hipFuncSetAttribute((const void*)x3p_kernel<L, A, WN, D, false, T, NT>,                               \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess);            \
-        (void)once;                                                                                                                \
-        RCOT_LAUNCH((x3p_kernel<L, A, WN, D, false, T, NT>), dim3(grid), dim3(256 * WN), smem, st, p);                      \
-    } while (0)
-    if (stat && add) X3P_LAUNCH(true, true, true);
-    else if (stat) X3P_LAUNCH(true, false, true);
-    else if (ln && add) X3P_LAUNCH(true, true, false);
-    else if (ln) X3P_LAUNCH(true, false, false);
-    else if (add) X3P_LAUNCH(false, true, false);
-    else X3P_LAUNCH(false, false, false);
-#undef X3P_LAUNCH
+    const bool L = ln || stat;
+    note_kernel("x3p_kernel<%s, %s, %d, %d, false, %s, %d>", tf(L), tf(add), WN, D, tf(stat), NT);
+    const dim3 g(grid), b(256 * WN);
+    if (stat && add) launch_lds<x3p_kernel<true, true, WN, D, false, true, NT>>(g, b, smem, st, p);
+    else if (stat) launch_lds<x3p_kernel<true, false, WN, D, false, true, NT>>(g, b, smem, st, p);
+    else if (ln && add) launch_lds<x3p_kernel<true, true, WN, D, false, false, NT>>(g, b, smem, st, p);
+    else if (ln) launch_lds<x3p_kernel<true, false, WN, D, false, false, NT>>(g, b, smem, st, p);
+    else if (add) launch_lds<x3p_kernel<false, true, WN, D, false, false, NT>>(g, b, smem, st, p);
+    else launch_lds<x3p_kernel<false, false, WN, D, false, false, NT>>(g, b, smem, st, p);
     RCOT_LAUNCH_CHECK();
     if (p.S > 1) {
         launch_p_reduce(p, Z, st);
@@ -716,17 +695,9 @@ int launch_pair(const P& p, const rcot_nt::NTP& q, int nA, size_t smemA, hipStre
     const int nB = q.tilesM * q.tilesN * q.S;
     const size_t smemB = sizeof(float) * (size_t)rcot_nt::NST * rcot_nt::STAGE;
     const size_t smem = smemA > smemB ? smemA : smemB;
-#define PAIR_LAUNCH(L)                                                                                                             \
-    do {                                                                                                                           \
-        note_kernel("x3p_nt_pair_kernel<%d, %d, %d, %d, %s>", TM, TN, WM, WNN, tf(L));                                             \
-        static bool once = (hipFuncSetAttribute((const void*)x3p_nt_pair_kernel<TM, TN, WM, WNN, L>,                               \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess);            \
-        (void)once;                                                                                                                \
-        RCOT_LAUNCH((x3p_nt_pair_kernel<TM, TN, WM, WNN, L>), dim3(nA + nB), dim3(256), smem, st, p, q, nA, nB);            \
-    } while (0)
-    if (q.mu) PAIR_LAUNCH(true);
-    else PAIR_LAUNCH(false);
-#undef PAIR_LAUNCH
+    note_kernel("x3p_nt_pair_kernel<%d, %d, %d, %d, %s>", TM, TN, WM, WNN, tf(q.mu != nullptr));
+    if (q.mu) launch_lds<x3p_nt_pair_kernel<TM, TN, WM, WNN, true>>(dim3(nA + nB), dim3(256), smem, st, p, q, nA, nB);
+    else launch_lds<x3p_nt_pair_kernel<TM, TN, WM, WNN, false>>(dim3(nA + nB), dim3(256), smem, st, p, q, nA, nB);
     RCOT_LAUNCH_CHECK();
     return RCOT_OK;
 }
@@ -755,35 +726,16 @@ int launch_conv(P p, hipStream_t st, size_t ws_bytes) {
     p.tilesN = p.N / (128 * WN);
     const int nk = cdiv(p.K, BK);
     const int base = p.tilesM * p.tilesN;
-    int S = 1;
-    if (p.ws && base * 2 <= slots && nk >= 16) {
-        S = slots / base;
-        if (S > nk / 8) S = nk / 8;
-        while (S > 1 && (size_t)S * p.M * p.N * sizeof(float) > ws_bytes) --S;
-        if (S < 1) S = 1;
-    }
-    p.kchunk = cdiv(nk, S);
-    p.S = cdiv(nk, p.kchunk);
-    if (p.S > 1 && nk - (p.S - 1) * p.kchunk < 2) {
-        p.kchunk = cdiv(nk, p.S - 1);
-        p.S = cdiv(nk, p.kchunk);
-    }
-    p.ntiles = base * p.S;
-    const int rounds = cdiv(p.ntiles, slots);
-    const int grid = cdiv(p.ntiles, rounds);
+    const int want = (p.ws && base * 2 <= slots && nk >= 16) ? slots / base : 1;
+    const SlabCut cut = cut_slabs(nk, base, want, (size_t)p.M * p.N * sizeof(float), ws_bytes);
+    p.S = cut.S; p.kchunk = cut.kchunk; p.ntiles = cut.ntiles;
     const size_t smem = (size_t)(D + 1) * 8192 + (size_t)(D + 2) * 8192 * WN;
-    static bool once = (hipFuncSetAttribute((const void*)x3p_kernel<false, false, WN, D, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            160 * 1024) == hipSuccess);
-    (void)once;
     note_kernel("x3p_kernel<false, false, %d, %d, true, false>", WN, D);
-    RCOT_LAUNCH((x3p_kernel<false, false, WN, D, true>), dim3(grid), dim3(256 * WN), smem, st, p);
+    launch_lds<x3p_kernel<false, false, WN, D, true>>(dim3(cut.grid(slots)), dim3(256 * WN), smem, st, p);
     RCOT_LAUNCH_CHECK();
     if (p.S > 1) {
-        const long per = (long)p.M * (p.N / 4);
-        long nb = (per + 255) / 256;
-        if (nb > 2048) nb = 2048;
-        RCOT_LAUNCH(x3w_conv_reduce_kernel, dim3((int)nb), dim3(256), 0, st, p.ws, p.S, p.M, p.N / 4, p.colmap, p.cbias, p.clrelu,
-                           p.ep.C, p.ep.ldc);
+        RCOT_LAUNCH(x3w_conv_reduce_kernel, dim3(slab_reduce_grid(p.M, p.N)), dim3(256), 0, st, p.ws, p.S, p.M, p.N / 4, p.colmap,
+                    p.cbias, p.clrelu, p.ep.C, p.ep.ldc);
         RCOT_LAUNCH_CHECK();
     }
     return RCOT_OK;
@@ -875,13 +827,10 @@ int pair_dgrad_wgrad_x3(const float* WP, long ldp, const void* WPs, const float*
         return NOT_ELIGIBLE;
     *S_out = q.S;
     *ld_out = q.ldws;
-    int rc;
-    if (cfg == 1) rc = launch_pair<1, 3, 4, 1>(p, q, nA, smemA, st);
-    else if (cfg == 2) rc = launch_pair<3, 1, 1, 4>(p, q, nA, smemA, st);
-    else if (cfg == 3) rc = launch_pair<1, 2, 4, 1>(p, q, nA, smemA, st);
-    else if (cfg == 4) rc = launch_pair<2, 1, 1, 4>(p, q, nA, smemA, st);
-    else if (cfg == 5) rc = launch_pair<1, 1, 2, 2>(p, q, nA, smemA, st);
-    else rc = launch_pair<2, 2, 2, 2>(p, q, nA, smemA, st);
+    const int rc = rcot_nt::with_nt_tile(cfg, [&](auto t) {
+        using T = decltype(t);
+        return launch_pair<T::TM, T::TN, T::WM, T::WN>(p, q, nA, smemA, st);
+    });
     if (rc != RCOT_OK) return rc;
     if (p.S > 1) {
         launch_p_reduce(p, B, st);
