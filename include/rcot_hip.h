@@ -25,7 +25,7 @@ extern "C" {
 
 /* Bumped on EVERY signature change; returned by rcot_abi_version() (csrc/api.hip) and compared by the loader
  * (rcot_amd/lib.py ABI_VERSION, tests/test_abi.py) so that a stale prebuilt .so is refused, not mis-called. */
-#define RCOT_ABI_VERSION 35
+#define RCOT_ABI_VERSION 36
 
 /* Arithmetic of the MFMA products of the three GEMM-shaped entry points that take `prec` (rcot_gemm_kmajor,
  * rcot_conv1x1_wgrad, rcot_bmm_nt); operands and results are fp32 in memory either way.
@@ -312,13 +312,6 @@ int rcot_attn_softmax(const float* Graw, int S, int ld, const float* sq, const f
 int rcot_attn_bwd_small(const float* dA, const float* A, const float* Gn, const float* sq, const float* temp,
                         float* dtemp_part, float* Eq, float* EqT, float* Dq, float* Dk, int B, int heads, int c,
                         void* stream);
-/* The backward of the attention-matrix chain of one block in TWO launches instead of four (c = 48 or 96): from dM
- * [B][C][C] (= dY V^T), W_o [C][C], A, Gn [B][heads][c][c], sq, temp it forms, per head block and row chunk, Mf =
- * W_o blockdiag(A) [B][C][C], the per-image dW_o [B][C][C] and partial dA = W_o^T dM (in ws), then everything
- * rcot_attn_bwd_small returns.  ws >= B*heads*ceil(C*c/3072)*c*c floats. */
-int rcot_attn_bwd_fused(const float* dM, const float* Wo, const float* A, const float* Gn, const float* sq, const float* temp,
-                        float* Mf, float* dWo_part, float* dtemp_part, float* Eq, float* EqT, float* Dq, float* Dk, int B,
-                        int heads, int c, void* ws, long ws_bytes, void* stream);
 /* The whole forward attention-matrix chain of one block for SMALL images (N = H*W a multiple of 256, N <= 4096: the 64x64,
  * 32x32 and 16x16 levels; c = 24, 48 or 96; C = heads*c a multiple of 16): from u = [q | k | v] [B][3C][N] (batch stride sUb)
  * it writes sq [B][2C] (|q_i|^2, |k_j|^2: F.normalize, Net_Restormer.py:39-40), Gn and A [B][heads][c][c] (:42-43) and the
@@ -330,10 +323,11 @@ int rcot_attn_bwd_fused(const float* dM, const float* Wo, const float* A, const 
 int rcot_attn_core_fwd(const float* u, long sUb, const float* temp, const float* WoT, long ldwt, float* sq, float* Gn, float* A,
                        float* MfT, long ldm, long sMb, int B, int heads, int c, int N, float* ws, size_t ws_bytes, void* stream);
 /* The backward of the attention-matrix chain of one block in ONE launch (c = 24, 48 or 96; C = heads*c a multiple of 16), one
- * workgroup per (head, image), the three small products on v_mfma_f32_16x16x4_f32 (exact fp32): everything rcot_attn_bwd_fused
- * returns — Mf = W_o blockdiag(A) [B][C][C], the per-image dW_o [B][C][C], dtau partials [B][heads], Eq / Eq^T [B][heads][c][c],
- * Dq / Dk [B][C] — from dM = dY V^T given dense (S = 0: [B][C][C]) or as S <= 8 split-K slabs [B][S][C][ldd] of
- * rcot_bmm_nt_slabs, summed here in a fixed order.  RCOT_EUNSUPPORTED for other head widths: rcot_attn_bwd_fused. */
+ * workgroup per (head, image), the three small products on v_mfma_f32_16x16x4_f32 (exact fp32): Mf = W_o blockdiag(A) [B][C][C],
+ * the per-image dW_o [B][C][C] and, from dA = W_o^T dM per head block, everything rcot_attn_bwd_small returns — dtau partials
+ * [B][heads], Eq / Eq^T [B][heads][c][c], Dq / Dk [B][C] — from dM = dY V^T given dense (S = 0: [B][C][C]) or as S <= 8 split-K
+ * slabs [B][S][C][ldd] of rcot_bmm_nt_slabs, summed here in a fixed order.  RCOT_EUNSUPPORTED for other head widths: three
+ * rcot_bmm_* calls + rcot_attn_bwd_small. */
 int rcot_attn_core_bwd(const float* dM, int S, int ldd, const float* Wo, const float* A, const float* Gn, const float* sq,
                        const float* temp, float* Mf, float* dWo_part, float* dtemp_part, float* Eq, float* EqT, float* Dq, float* Dk, int B,
                        int heads, int c, void* stream);

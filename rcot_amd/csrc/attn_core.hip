@@ -19,16 +19,21 @@ using namespace rcot;
 
 namespace {
 
-__device__ __forceinline__ float clamp_norm(float sumsq) { return fmaxf(sqrtf(sumsq), 1e-12f); }
+template <int CT>                                   // channels per head padded to 16 CT (c = 24 -> 2, 48 -> 3, 96 -> 6)
+struct AHead {
+    static constexpr int cp = 16 * CT;
+    static constexpr int c = CT == 2 ? 24 : cp;                   // the head widths of T_net (compile-time: every bound check folds)
+    static constexpr int LDA = (cp % 32 == 16) ? cp : cp + 16;    // == 16 (mod 32): the 4 k-rows x 16 columns of an MFMA operand hit 64 banks
+};
 
 // These kernels run once per wavefront through code that a cold instruction cache has to fetch: they are written for FEW
 // instructions (rolled loops wherever the data does not have to be in flight at once, no integer divisions) — a first, fully
 // unrolled version (3500 instructions) spent 12 us per launch before doing any work.
-template <int CT>                                   // channels per head padded to 16 CT (c = 24 -> 2, 48 -> 3, 96 -> 6)
-struct AC {
-    static constexpr int cp = 16 * CT;
-    static constexpr int c = CT == 2 ? 24 : cp;                   // the head widths of T_net (compile-time: every bound check folds)
-    static constexpr int LDA = (cp % 32 == 16) ? cp : cp + 16;    // == 16 (mod 32): the 4 k-rows x 16 columns of an MFMA operand hit 64 banks
+template <int CT>
+struct AC : AHead<CT> {
+    using AHead<CT>::cp;
+    using AHead<CT>::c;
+    using AHead<CT>::LDA;
     static constexpr int PX = CT == 6 ? 128 : 256;                // pixels per LDS chunk
     static constexpr int Q4 = PX / 4;
     static constexpr int LDQ = PX + 8;                            // == 8 (mod 64): conflict-free ds_read_b128 of 16 rows x 4 pixel quads
@@ -365,21 +370,106 @@ int launch_core_fwd(const float* u, long sUb, const float* temp, const float* Wo
 //     dW_o part[b][:, head blk] = D A^T
 //     dA                        = W^T D          (c x c, summed over all C rows in registers)
 //     dS = A.(dA - rowsum(dA.A));  dtau part = sum dS.Gn;  Eq = tau dS / (|q| |k|^T), Eq^T;  Dq, Dk
-// replaces attn_bwd_chunk_kernel (one workgroup per row chunk, scalar FMAs from LDS: 17-33 us) + attn_bwd_small_kernel
-// (10-50 us) and, with slabs, the reduce launch of dM.  The three products run on v_mfma_f32_16x16x4_f32 (exact fp32): a
-// wavefront walks 16-row tiles of W and D staged in its own LDS slice and keeps its share of dA in registers.
+// replaces three products on scalar FMAs + attn_bwd_small_kernel (27-83 us together) and, with slabs, the reduce launch of dM.
+// The three products run on v_mfma_f32_16x16x4_f32 (exact fp32): a wavefront walks 16-row tiles of W and D staged in its own
+// LDS slice and keeps its share of dA in registers.
 template <int CT>
-struct AB {
-    static constexpr int cp = 16 * CT;
-    static constexpr int c = CT == 2 ? 24 : cp;
-    static constexpr int LDA = (cp % 32 == 16) ? cp : cp + 16;      // A / A^T as B operands: == 16 (mod 32)
+struct AB : AHead<CT> {
+    using AHead<CT>::cp;
+    using AHead<CT>::c;
+    using AHead<CT>::LDA;                                           // A / A^T as B operands
     static constexpr int LD = cp + 2;                               // 16-row W / D tiles as A operands: LD/2 odd
     static constexpr int NW = 4, NT = 256;
+    static constexpr int NEL = (cp * cp + NT - 1) / NT;             // elements of a padded c x c block per thread
     static constexpr int Q4 = c / 4;                                // 16-byte pieces per tile row
     static constexpr int NLD = (16 * Q4 + 63) / 64;                 // pieces per lane and tile
     static_assert(NW * 2 * 16 * LD >= cp * LDA, "Gn is staged in the tile region for the tail");
     static constexpr size_t smem = sizeof(float) * (size_t)(2 * cp * LDA + NW * 2 * 16 * LD + 2 * cp + 8);
 };
+
+// ---- what the one-launch kernel and the row-group kernel share: the piece map of a 16-row tile, a wavefront's tile of W and D
+// from registers into its LDS slice, and the three MFMA products of a tile.  Each kernel's own: how the slabs of dM are fetched
+// and added, how the four wavefronts' shares of dA meet, the softmax-backward tail — and the staging of A / A^T (NEL elements
+// per thread), the same few lines in both: as a shared inline it moved the register counts of both kernels (NOTES, "After round 6").
+
+// Piece q of a lane of a 16-row tile: floats 4 c4 .. 4 c4 + 3 of row r; false where the lane has no such piece (c = 24 only).
+template <int CT>
+__device__ __forceinline__ bool tile_piece(int q, int& r, int& c4) {
+    constexpr int Q4 = AB<CT>::Q4;
+    const int lane = threadIdx.x & 63, idx = lane + 64 * q;
+    r = idx / Q4;
+    c4 = idx - r * Q4;
+    return (16 * Q4) % 64 == 0 || idx < 16 * Q4;
+}
+
+// This wavefront's 16 rows of W and D from registers to its LDS slice, 8-byte stores (LD is even), and zeros in the padding
+// columns of the tiles (c = 24).
+template <int CT>
+__device__ __forceinline__ void tile_stage(float* Wt, float* Dt, const f32x4 (&wv)[AB<CT>::NLD], const f32x4 (&dv)[AB<CT>::NLD]) {
+    constexpr int cp = AB<CT>::cp, c = AB<CT>::c, LD = AB<CT>::LD;
+#pragma unroll
+    for (int q = 0; q < AB<CT>::NLD; ++q) {
+        int r, c4;
+        if (tile_piece<CT>(q, r, c4)) {
+            float* wd = Wt + r * LD + 4 * c4;
+            float* dd = Dt + r * LD + 4 * c4;
+            *reinterpret_cast<float2*>(wd) = make_float2(wv[q][0], wv[q][1]);
+            *reinterpret_cast<float2*>(wd + 2) = make_float2(wv[q][2], wv[q][3]);
+            *reinterpret_cast<float2*>(dd) = make_float2(dv[q][0], dv[q][1]);
+            *reinterpret_cast<float2*>(dd + 2) = make_float2(dv[q][2], dv[q][3]);
+        }
+    }
+    if (c < cp) {
+        for (int e = threadIdx.x & 63; e < 16 * (cp - c); e += 64) {
+            const int r = e / (cp - c), x = c + e - r * (cp - c);
+            Wt[r * LD + x] = 0.f;
+            Dt[r * LD + x] = 0.f;
+        }
+    }
+}
+
+// The products of tile mt from LDS: rows 16 mt .. + 15 of Mf = W A and of the dW_o part = D A^T (Mfh, dWh: this image's and
+// head's column block, row stride C), and dacc += W^T D over the tile's rows.
+template <int CT>
+__device__ __forceinline__ void tile_products(f32x4 (&dacc)[CT][CT], const float* Wt, const float* Dt, const float* As,
+                                              const float* ATs, float* Mfh, float* dWh, int mt, int C) {
+    constexpr int cp = AB<CT>::cp, c = AB<CT>::c, LDA = AB<CT>::LDA, LD = AB<CT>::LD;
+    const int lane = threadIdx.x & 63, r16 = lane & 15, kq = lane >> 4;
+    // Mf tile = W A and dW_o tile = D A^T: D[m][n], A operand lane (m = r16, k = 4 s + kq), B operand lane (k, n = r16)
+#pragma unroll 1
+    for (int nt = 0; nt < CT; ++nt) {
+        f32x4 a1 = {0.f, 0.f, 0.f, 0.f}, a2 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s_ = 0; s_ < cp / 4; ++s_) {
+            const int k = 4 * s_ + kq;
+            a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(Wt[r16 * LD + k], As[k * LDA + 16 * nt + r16], a1, 0, 0, 0);
+            a2 = __builtin_amdgcn_mfma_f32_16x16x4f32(Dt[r16 * LD + k], ATs[k * LDA + 16 * nt + r16], a2, 0, 0, 0);
+        }
+        const int n = 16 * nt + r16;
+        if (n < c) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const long m = 16 * mt + 4 * kq + r;
+                Mfh[m * C + n] = a1[r];
+                dWh[m * C + n] = a2[r];
+            }
+        }
+    }
+    // dA += W^T D over the 16 rows: D[i][j], A operand lane (i = 16 it + r16, k = m = 4 s + kq), B operand lane (m, j)
+#pragma unroll
+    for (int s_ = 0; s_ < 4; ++s_) {
+        float wa[CT], db[CT];
+#pragma unroll
+        for (int t = 0; t < CT; ++t) {
+            wa[t] = Wt[(4 * s_ + kq) * LD + 16 * t + r16];
+            db[t] = Dt[(4 * s_ + kq) * LD + 16 * t + r16];
+        }
+#pragma unroll
+        for (int i = 0; i < CT; ++i)
+#pragma unroll
+            for (int j = 0; j < CT; ++j) dacc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[i], db[j], dacc[i][j], 0, 0, 0);
+    }
+}
 
 template <int CT>
 __global__ __launch_bounds__(256) void attn_bwd_core_kernel(const float* __restrict__ dM, int S, long ldd, long sDs, long sDb,
@@ -390,7 +480,7 @@ __global__ __launch_bounds__(256) void attn_bwd_core_kernel(const float* __restr
                                                             float* __restrict__ Eq, float* __restrict__ EqT, float* __restrict__ Dq,
                                                             float* __restrict__ Dk, int heads) {
     using K = AB<CT>;
-    constexpr int cp = K::cp, c = K::c, LDA = K::LDA, LD = K::LD, NW = K::NW, NT = K::NT, Q4 = K::Q4, NLD = K::NLD;
+    constexpr int cp = K::cp, c = K::c, LDA = K::LDA, LD = K::LD, NW = K::NW, NT = K::NT, NLD = K::NLD;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* As = sm;                               // A [i][j]
     float* ATs = As + cp * LDA;                   // A^T [j][i]; after the row loop: the dA accumulator
@@ -403,10 +493,9 @@ __global__ __launch_bounds__(256) void attn_bwd_core_kernel(const float* __restr
     const long off = ((long)b * heads + h) * c * c;
     // ---- A and A^T, zero padded; Gn rides along in registers until the tail.  ALL loads of a thread are issued before the first
     // store (a loop that loads and stores element by element chains one memory latency per trip: 9-36 of them here)
-    constexpr int NEL = (cp * cp + NT - 1) / NT;
-    float av[NEL], gv[NEL];
+    float av[K::NEL], gv[K::NEL];
 #pragma unroll
-    for (int q = 0; q < NEL; ++q) {
+    for (int q = 0; q < K::NEL; ++q) {
         const int e = tid + q * NT;
         const int i = e / cp, j = e - i * cp;
         const bool ok = e < cp * cp && i < c && j < c;
@@ -414,7 +503,7 @@ __global__ __launch_bounds__(256) void attn_bwd_core_kernel(const float* __restr
         gv[q] = ok ? Gn[off + i * c + j] : 0.f;
     }
 #pragma unroll
-    for (int q = 0; q < NEL; ++q) {
+    for (int q = 0; q < K::NEL; ++q) {
         const int e = tid + q * NT;
         const int i = e / cp, j = e - i * cp;
         if (e < cp * cp) {
@@ -442,9 +531,8 @@ __global__ __launch_bounds__(256) void attn_bwd_core_kernel(const float* __restr
     auto fetch = [&](int mt) {
 #pragma unroll
         for (int q = 0; q < NLD; ++q) {
-            const int idx = lane + 64 * q;
-            const int r = idx / Q4, c4 = idx - r * Q4;
-            const bool ok = idx < 16 * Q4 && mt < nmt;
+            int r, c4;
+            const bool ok = tile_piece<CT>(q, r, c4) && mt < nmt;
             const long m = 16 * mt + r;
             wv[q] = ok ? *reinterpret_cast<const f32x4*>(Wh + m * C + 4 * c4) : f32x4{0.f, 0.f, 0.f, 0.f};
             f32x4 d = ok ? *reinterpret_cast<const f32x4*>(Dh + m * ldd + 4 * c4) : f32x4{0.f, 0.f, 0.f, 0.f};
@@ -456,64 +544,12 @@ __global__ __launch_bounds__(256) void attn_bwd_core_kernel(const float* __restr
     fetch(wave);
 #pragma unroll 1
     for (int mt = wave; mt < nmt; mt += NW) {
-        // stage this wavefront's 16 rows of W and D (the slabs of D summed in a fixed order); 8-byte LDS stores (LD is even)
-#pragma unroll
-        for (int q = 0; q < NLD; ++q) {
-            const int idx = lane + 64 * q;
-            const int r = idx / Q4, c4 = idx - r * Q4;
-            if (idx < 16 * Q4) {
-                float* wd = Wt + r * LD + 4 * c4;
-                float* dd = Dt + r * LD + 4 * c4;
-                *reinterpret_cast<float2*>(wd) = make_float2(wv[q][0], wv[q][1]);
-                *reinterpret_cast<float2*>(wd + 2) = make_float2(wv[q][2], wv[q][3]);
-                *reinterpret_cast<float2*>(dd) = make_float2(dv[q][0], dv[q][1]);
-                *reinterpret_cast<float2*>(dd + 2) = make_float2(dv[q][2], dv[q][3]);
-            }
-        }
+        // stage this wavefront's 16 rows of W and D (the slabs of D summed in a fixed order)
+        tile_stage<CT>(Wt, Dt, wv, dv);
         fetch(mt + NW);
-        if (c < cp) {                                                        // padding columns of the tiles (c = 24)
-            for (int e = lane; e < 16 * (cp - c); e += 64) {
-                const int r = e / (cp - c), x = c + e - r * (cp - c);
-                Wt[r * LD + x] = 0.f;
-                Dt[r * LD + x] = 0.f;
-            }
-        }
         // (own LDS slice, own lanes: wavefront-level ordering only — the compiler's lgkmcnt covers the store -> load order)
         __builtin_amdgcn_wave_barrier();
-        // Mf tile = W A and dW_o tile = D A^T: D[m][n], A operand lane (m = r16, k = 4 s + kq), B operand lane (k, n = r16)
-#pragma unroll 1
-        for (int nt = 0; nt < CT; ++nt) {
-            f32x4 a1 = {0.f, 0.f, 0.f, 0.f}, a2 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int s_ = 0; s_ < cp / 4; ++s_) {
-                const int k = 4 * s_ + kq;
-                a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(Wt[r16 * LD + k], As[k * LDA + 16 * nt + r16], a1, 0, 0, 0);
-                a2 = __builtin_amdgcn_mfma_f32_16x16x4f32(Dt[r16 * LD + k], ATs[k * LDA + 16 * nt + r16], a2, 0, 0, 0);
-            }
-            const int n = 16 * nt + r16;
-            if (n < c) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const long m = 16 * mt + 4 * kq + r;
-                    Mfh[m * C + n] = a1[r];
-                    dWh[m * C + n] = a2[r];
-                }
-            }
-        }
-        // dA += W^T D over the 16 rows: D[i][j], A operand lane (i = 16 it + r16, k = m = 4 s + kq), B operand lane (m, j)
-#pragma unroll
-        for (int s_ = 0; s_ < 4; ++s_) {
-            float wa[CT], db[CT];
-#pragma unroll
-            for (int t = 0; t < CT; ++t) {
-                wa[t] = Wt[(4 * s_ + kq) * LD + 16 * t + r16];
-                db[t] = Dt[(4 * s_ + kq) * LD + 16 * t + r16];
-            }
-#pragma unroll
-            for (int i = 0; i < CT; ++i)
-#pragma unroll
-                for (int j = 0; j < CT; ++j) dacc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[i], db[j], dacc[i][j], 0, 0, 0);
-        }
+        tile_products<CT>(dacc, Wt, Dt, As, ATs, Mfh, dWh, mt, C);
         __builtin_amdgcn_wave_barrier();
     }
     // ---- dA: the wavefronts add their shares into the A^T region one after the other (fixed order)
@@ -537,7 +573,7 @@ __global__ __launch_bounds__(256) void attn_bwd_core_kernel(const float* __restr
     // ---- the c x c tail: a row per 16-lane group, CT columns per lane.  Gn goes to the (now free) tile region first.
     float* Gs = tiles;
 #pragma unroll
-    for (int q = 0; q < NEL; ++q) {
+    for (int q = 0; q < K::NEL; ++q) {
         const int e = tid + q * NT;
         const int i = e / cp, j = e - i * cp;
         if (e < cp * cp) Gs[i * LDA + j] = gv[q];
@@ -580,10 +616,7 @@ __global__ __launch_bounds__(256) void attn_bwd_core_kernel(const float* __restr
         part += rs_;
 #pragma unroll
         for (int o = 8; o > 0; o >>= 1) rs_ += __shfl_xor(rs_, o, 64);
-        if (gl == 0 && i < c) {
-            const float q2 = sqq[i];
-            Dq[(long)b * C + h * c + i] = q2 >= 1e-24f ? -tau * rs_ / q2 : 0.f;
-        }
+        if (gl == 0 && i < c) Dq[(long)b * C + h * c + i] = norm_bwd_scale(tau, rs_, sqq[i]);
     }
     part = block_sum<256>(part, red);                                       // (its barriers also publish As / dAs)
     if (tid == 0) dtemp_part[(long)b * heads + h] = part;
@@ -600,10 +633,7 @@ __global__ __launch_bounds__(256) void attn_bwd_core_kernel(const float* __restr
         }
 #pragma unroll
         for (int o = 8; o > 0; o >>= 1) cs_ += __shfl_xor(cs_, o, 64);
-        if (gl == 0) {
-            const float k2 = sqk[i];
-            Dk[(long)b * C + h * c + i] = k2 >= 1e-24f ? -tau * cs_ / k2 : 0.f;
-        }
+        if (gl == 0) Dk[(long)b * C + h * c + i] = norm_bwd_scale(tau, cs_, sqk[i]);
     }
 }
 
@@ -646,7 +676,7 @@ __global__ __launch_bounds__(256) void attn_rows_kernel(const float* __restrict_
                                                         float* __restrict__ Mf, float* __restrict__ dWo_part,
                                                         float* __restrict__ dA_part, int heads, int tpg) {
     using K = AB<CT>;
-    constexpr int cp = K::cp, c = K::c, LDA = K::LDA, LD = K::LD, NW = K::NW, NT = K::NT, Q4 = K::Q4, NLD = K::NLD, LDS = AR<CT>::LDS;
+    constexpr int cp = K::cp, c = K::c, LDA = K::LDA, LD = K::LD, NW = K::NW, NLD = K::NLD, LDS = AR<CT>::LDS;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* As = sm;                               // A [i][j]
     float* ATs = As + cp * LDA;                   // A^T [j][i]
@@ -663,11 +693,10 @@ __global__ __launch_bounds__(256) void attn_rows_kernel(const float* __restrict_
     float* dWh = dWo_part + (long)b * C * C + h * c;
     // ---- ALL loads of a thread before its first store: A, then this wavefront's tile of W and D (wavefront w takes tile t0 + w: with
     // one tile per wavefront there is no trip to fetch ahead for; a wavefront past the group's end loads nothing and adds zeros)
-    constexpr int NEL = (cp * cp + NT - 1) / NT;
-    float av[NEL];
+    float av[K::NEL];
 #pragma unroll
-    for (int q = 0; q < NEL; ++q) {
-        const int e = tid + q * NT;
+    for (int q = 0; q < K::NEL; ++q) {
+        const int e = tid + q * K::NT;
         const int i = e / cp, j = e - i * cp;
         av[q] = (e < cp * cp && i < c && j < c) ? A[off + i * c + j] : 0.f;
     }
@@ -675,14 +704,12 @@ __global__ __launch_bounds__(256) void attn_rows_kernel(const float* __restrict_
     const bool live = mt < t1;                                           // wave-uniform
     const float* Wm = Wh + (long)(live ? mt : t0) * 16 * C;
     const float* Dm = Dh + (long)(live ? mt : t0) * 16 * ldd;
-    // piece q of a lane: floats 4 c4 .. 4 c4 + 3 of row r of the tile (every lane has NLD pieces except at c = 24)
     int wo[NLD], dof[NLD];
     f32x4 wv[NLD], dv[NLD];
 #pragma unroll
     for (int q = 0; q < NLD; ++q) {
-        const int idx = lane + 64 * q;
-        const int r = idx / Q4, c4 = idx - r * Q4;
-        const bool ok = live && ((16 * Q4) % 64 == 0 || idx < 16 * Q4);
+        int r, c4;
+        const bool ok = tile_piece<CT>(q, r, c4) && live;
         wo[q] = ok ? r * C + 4 * c4 : -1;
         dof[q] = r * (int)ldd + 4 * c4;
         wv[q] = ok ? *reinterpret_cast<const f32x4*>(Wm + wo[q]) : f32x4{0.f, 0.f, 0.f, 0.f};
@@ -705,8 +732,8 @@ __global__ __launch_bounds__(256) void attn_rows_kernel(const float* __restrict_
             for (int q = 0; q < NLD; ++q) dv[q] += x[u][q];
     }
 #pragma unroll
-    for (int q = 0; q < NEL; ++q) {
-        const int e = tid + q * NT;
+    for (int q = 0; q < K::NEL; ++q) {
+        const int e = tid + q * K::NT;
         const int i = e / cp, j = e - i * cp;
         if (e < cp * cp) {
             As[i * LDA + j] = av[q];
@@ -716,69 +743,14 @@ __global__ __launch_bounds__(256) void attn_rows_kernel(const float* __restrict_
     const int r16 = lane & 15, kq = lane >> 4;
     float* Wt = tiles + wave * 2 * 16 * LD;
     float* Dt = Wt + 16 * LD;
-    // stage this wavefront's 16 rows of W and D; 8-byte LDS stores (LD is even)
-#pragma unroll
-    for (int q = 0; q < NLD; ++q) {
-        const int idx = lane + 64 * q;
-        const int r = idx / Q4, c4 = idx - r * Q4;
-        if ((16 * Q4) % 64 == 0 || idx < 16 * Q4) {
-            float* wd = Wt + r * LD + 4 * c4;
-            float* dd = Dt + r * LD + 4 * c4;
-            *reinterpret_cast<float2*>(wd) = make_float2(wv[q][0], wv[q][1]);
-            *reinterpret_cast<float2*>(wd + 2) = make_float2(wv[q][2], wv[q][3]);
-            *reinterpret_cast<float2*>(dd) = make_float2(dv[q][0], dv[q][1]);
-            *reinterpret_cast<float2*>(dd + 2) = make_float2(dv[q][2], dv[q][3]);
-        }
-    }
-    if (c < cp) {                                                        // padding columns of the tiles (c = 24)
-        for (int e = lane; e < 16 * (cp - c); e += 64) {
-            const int r = e / (cp - c), x = c + e - r * (cp - c);
-            Wt[r * LD + x] = 0.f;
-            Dt[r * LD + x] = 0.f;
-        }
-    }
+    tile_stage<CT>(Wt, Dt, wv, dv);
     __syncthreads();                                                     // A and A^T are complete (and every wavefront's own tile)
     f32x4 dacc[CT][CT];
 #pragma unroll
     for (int i = 0; i < CT; ++i)
 #pragma unroll
         for (int j = 0; j < CT; ++j) dacc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (live) {
-        // Mf tile = W A and dW_o tile = D A^T: D[m][n], A operand lane (m = r16, k = 4 s + kq), B operand lane (k, n = r16)
-#pragma unroll 1
-        for (int nt = 0; nt < CT; ++nt) {
-            f32x4 a1 = {0.f, 0.f, 0.f, 0.f}, a2 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int s_ = 0; s_ < cp / 4; ++s_) {
-                const int k = 4 * s_ + kq;
-                a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(Wt[r16 * LD + k], As[k * LDA + 16 * nt + r16], a1, 0, 0, 0);
-                a2 = __builtin_amdgcn_mfma_f32_16x16x4f32(Dt[r16 * LD + k], ATs[k * LDA + 16 * nt + r16], a2, 0, 0, 0);
-            }
-            const int n = 16 * nt + r16;
-            if (n < c) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const long m = 16 * mt + 4 * kq + r;
-                    Mfh[m * C + n] = a1[r];
-                    dWh[m * C + n] = a2[r];
-                }
-            }
-        }
-        // dA = W^T D over the 16 rows: D[i][j], A operand lane (i = 16 it + r16, k = m = 4 s + kq), B operand lane (m, j)
-#pragma unroll
-        for (int s_ = 0; s_ < 4; ++s_) {
-            float wa[CT], db[CT];
-#pragma unroll
-            for (int t = 0; t < CT; ++t) {
-                wa[t] = Wt[(4 * s_ + kq) * LD + 16 * t + r16];
-                db[t] = Dt[(4 * s_ + kq) * LD + 16 * t + r16];
-            }
-#pragma unroll
-            for (int i = 0; i < CT; ++i)
-#pragma unroll
-                for (int j = 0; j < CT; ++j) dacc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[i], db[j], dacc[i][j], 0, 0, 0);
-        }
-    }
+    if (live) tile_products<CT>(dacc, Wt, Dt, As, ATs, Mfh, dWh, mt, C);
     // ---- dA: the four shares side by side in LDS (over A, A^T and the tiles, which nobody reads any more), then one pass
     __syncthreads();
     float* sh = sm + wave * cp * LDS + (4 * kq) * LDS + r16;
@@ -933,7 +905,7 @@ __global__ __launch_bounds__(256) void attn_rows_tail_kernel(const float* __rest
         row_store<CT>(Eh + (e0 + 16 * c * rr), e, ok);
         part += rs_;
         rs_ = row16_sum(rs_);
-        if (gl == 0 && (!PAD || grp + 16 * rr < c)) Dq[(long)b * C + h * c + grp + 16 * rr] = q2[rr] >= 1e-24f ? -tau * rs_ / q2[rr] : 0.f;
+        if (gl == 0 && (!PAD || grp + 16 * rr < c)) Dq[(long)b * C + h * c + grp + 16 * rr] = norm_bwd_scale(tau, rs_, q2[rr]);
     }
 #pragma unroll
     for (int t = 0; t < CT; ++t) {
@@ -945,8 +917,7 @@ __global__ __launch_bounds__(256) void attn_rows_tail_kernel(const float* __rest
     if (tid == 0) dtemp_part[z] = part;
     if (tid < c) {
         const float s = ((csw[0][tid] + csw[1][tid]) + csw[2][tid]) + csw[3][tid];
-        const float kk = sqk[tid];
-        Dk[(long)b * C + h * c + tid] = kk >= 1e-24f ? -tau * s / kk : 0.f;
+        Dk[(long)b * C + h * c + tid] = norm_bwd_scale(tau, s, sqk[tid]);
     }
 }
 

@@ -75,6 +75,12 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
     return t;
 }
 
+// F.normalize (MDTA's q and k rows): |x| from the row's sum of squares, clamped as torch does.
+__device__ __forceinline__ float clamp_norm(float sumsq) { return fmaxf(sqrtf(sumsq), 1e-12f); }
+
+// Its backward's diagonal term, dx += D x with D = -tau s / |x|^2 (s: the row's sum of dS.Gn); zero where the forward clamped.
+__device__ __forceinline__ float norm_bwd_scale(float tau, float s, float sumsq) { return sumsq >= 1e-24f ? -tau * s / sumsq : 0.f; }
+
 // Fixed-order totals of per-workgroup partials, for ONE workgroup of 256 threads: ND streams of nb fp64 values (stream d at
 // part_d[d * nb ..)) and one stream of nb int64 values.  Strided per-thread sums (the loads of eight steps in flight, the sums in
 // order), then a tree over the 256 threads; every thread returns with the totals.

@@ -9,7 +9,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 35     # == RCOT_ABI_VERSION in include/rcot_hip.h (checked by tests/test_abi.py and at load time)
+ABI_VERSION = 36     # == RCOT_ABI_VERSION in include/rcot_hip.h (checked by tests/test_abi.py and at load time)
 PREC_FP32, PREC_BF16X3, PREC_BF16X6, PREC_BF16X1 = 0, 1, 2, 3     # RCOT_PREC_* of include/rcot_hip.h
 LIB_PATH = os.environ.get("RCOT_LIB") or os.path.join(_HERE, "librcot_hip.so")   # RCOT_LIB: A/B builds while tuning
 
@@ -87,7 +87,6 @@ SIGNATURES = {
     "rcot_row_sumsq": [_f, _f, _i, _i, _i, _l, _f],
     "rcot_attn_softmax": [_f, _i, _i, _f, _f, _f, _f, _i, _i, _i, _f],
     "rcot_attn_bwd_small": [_f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _f],
-    "rcot_attn_bwd_fused": [_f] * 13 + [_i, _i, _i, _f, _l, _f],
     "rcot_attn_core_fwd": [_f, _l, _f, _f, _l, _f, _f, _f, _f, _l, _l, _i, _i, _i, _i, _f, _sz, _f],
     "rcot_attn_core_bwd": [_f, _i, _i] + [_f] * 12 + [_i, _i, _i, _f],
     "rcot_attn_rows_bwd": [_f, _i, _i] + [_f] * 12 + [_i, _i, _i, _i, _f, _sz, _f],

@@ -294,10 +294,7 @@ class TransformerBlockOp:
         Dq, Dk = be.empty(B, C), be.empty(B, C)
         if be.attn_core_bwd(dM, self.Wo, A, Gn, sq, self.temp, Mf, dWo_part, dtemp_part, Eq, EqT, Dq, Dk):
             pass        # Mf = W_o blockdiag(A), dW_o (per image), dA = W_o^T dM and the softmax backward: fp32 MFMA, row groups + tail or ONE launch
-        elif be.attn_fused_ok(c):
-            # the same as two launches (row chunks, then the c x c tail)
-            be.attn_bwd_fused(dM, self.Wo, A, Gn, sq, self.temp, Mf, dWo_part, dtemp_part, Eq, EqT, Dq, Dk)
-        else:
+        else:           # head widths other than 24 / 48 / 96: the three products one by one, then the c x c tail
             be.bmm_nn(self._wo_heads(B), A, self._head_cols(Mf))     # Mf = W_o blockdiag(A): K-major operand of dV = Mf^T dY
             dA = be.empty(B, hd, c, c)
             dMh = self._head_cols(dM)

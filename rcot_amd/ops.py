@@ -1132,16 +1132,6 @@ class HipBackend:
                                               dtemp_part.data_ptr(), Eq.data_ptr(), EqT.data_ptr(), Dq.data_ptr(), Dk.data_ptr(), B, heads,
                                               c, self._st()), "rcot_attn_bwd_small")
 
-    def attn_bwd_fused(self, dM, Wo, A, Gn, sq, temp, Mf, dWo_part, dtemp_part, Eq, EqT, Dq, Dk):
-        """Mf = W_o blockdiag(A), per-image dW_o, and the outputs of attn_bwd_small: two launches instead of four."""
-        B, heads, c, _ = A.shape
-        for t in (dM, Wo, A, Gn, sq, temp, Mf, dWo_part, dtemp_part, Eq, EqT, Dq, Dk):
-            assert t.is_contiguous()
-        _lib.check(self.L.rcot_attn_bwd_fused(dM.data_ptr(), Wo.data_ptr(), A.data_ptr(), Gn.data_ptr(), sq.data_ptr(),
-                                              temp.data_ptr(), Mf.data_ptr(), dWo_part.data_ptr(), dtemp_part.data_ptr(),
-                                              Eq.data_ptr(), EqT.data_ptr(), Dq.data_ptr(), Dk.data_ptr(), B, heads, c,
-                                              self.ws.data_ptr(), self.ws_bytes, self._st()), "rcot_attn_bwd_fused")
-
     # "auto": the measured rule of attn_rows_route(); "on" / "off": every head width / none (tests and scripts/bench_attn_rows.py
     # compare the two forms through this wrapper)
     attn_rows = "auto"
@@ -1169,9 +1159,10 @@ class HipBackend:
         return c == 96 or (c == 48 and heads >= 2)
 
     def attn_core_bwd(self, dM, Wo, A, Gn, sq, temp, Mf, dWo_part, dtemp_part, Eq, EqT, Dq, Dk) -> bool:
-        """Everything attn_bwd_fused returns, from rcot_attn_rows_bwd (two launches on many workgroups) where attn_rows_route()
-        says so, else in ONE launch (rcot_attn_core_bwd).  ``dM``: the dense [B, C, C] tensor or the slab descriptor (pointer, S,
-        ld) of bmm_nt_slabs (any S for the row-group form, S <= 8 for the one-launch form).  False when neither takes the shape."""
+        """Mf = W_o blockdiag(A), the per-image dW_o and the outputs of attn_bwd_small, from rcot_attn_rows_bwd (two launches on
+        many workgroups) where attn_rows_route() says so, else in ONE launch (rcot_attn_core_bwd).  ``dM``: the dense [B, C, C]
+        tensor or the slab descriptor (pointer, S, ld) of bmm_nt_slabs (any S for the row-group form, S <= 8 for the one-launch
+        form).  False when neither takes the shape: the caller runs the three products and attn_bwd_small."""
         B, heads, c, _ = A.shape
         for t in (Wo, A, Gn, sq, temp, Mf, dWo_part, dtemp_part, Eq, EqT, Dq, Dk):
             assert t.is_contiguous()
@@ -1195,7 +1186,7 @@ class HipBackend:
                 return False
             _lib.check(rc, "rcot_attn_rows_bwd")
             return True
-        if c > 48 or S > 8:
+        if S > 8:
             return False
         rc = self.L.rcot_attn_core_bwd(dp, S, ld, Wo.data_ptr(), A.data_ptr(), Gn.data_ptr(), sq.data_ptr(), temp.data_ptr(),
                                        Mf.data_ptr(), dWo_part.data_ptr(), dtemp_part.data_ptr(), Eq.data_ptr(), EqT.data_ptr(),
@@ -1204,10 +1195,6 @@ class HipBackend:
             return False
         _lib.check(rc, "rcot_attn_core_bwd")
         return True
-
-    @staticmethod
-    def attn_fused_ok(c: int) -> bool:
-        return c in (48, 96)
 
     def batch_reduce(self, src, dst, beta: float = 1.0):
         """dst = beta*dst + src.sum(0); src: [B, ...] contiguous."""

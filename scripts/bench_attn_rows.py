@@ -1,7 +1,7 @@
 """Kernel-level timing of the attention-matrix backward behind its own dM product, exact fp32, B = 8, the (c, heads, C, plane) of the
-transport map's levels: the route of the one-launch / two-launch forms (rcot_bmm_nt with its reduce launch, then rcot_attn_core_bwd
-or rcot_attn_bwd_fused) against the row-group form (rcot_attn_rows_bwd; up to 32x32 behind rcot_bmm_nt_slabs: the slabs the product
-really chooses at that level go straight into the row-group kernel).  Every launch is timed by the library's own per-launch device time
+transport map's levels: the one-launch form (attn_rows = "off": rcot_bmm_nt with its reduce launch, then rcot_attn_core_bwd at every
+head width) against the row-group form (rcot_attn_rows_bwd; up to 32x32 behind rcot_bmm_nt_slabs: the slabs the product really
+chooses at that level go straight into the row-group kernel).  Every launch is timed by the library's own per-launch device time
 stamps (rcot_profile_begin / _end); the operands of the measured kernels were written by the launch before them or belong to
 another of NSETS rotating sets, never to the previous repetition.
     python scripts/bench_attn_rows.py [reps]"""
@@ -20,7 +20,7 @@ be.prec = lib.PREC_FP32
 B, NSETS = int(os.environ.get("BT_BATCH", "8")), 16
 REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 48
 LEVELS = [(48, 1, 128), (96, 1, 128), (48, 2, 64), (48, 4, 32), (48, 8, 16), (96, 4, 16)]          # c, heads, plane side
-WATCH = ("nt_reduce", "attn_bwd_core", "attn_bwd_chunk", "attn_bwd_small", "attn_rows")
+WATCH = ("nt_reduce", "attn_bwd_core", "attn_rows")
 
 
 def profile(fn):
@@ -65,12 +65,11 @@ for c, heads, side in LEVELS:
             assert be.attn_core_bwd(dM, Wo, A, Gn, sq, temp, *outs)
         else:
             be.bmm_nt(dy, V, dM.unsqueeze(1))
-            if not be.attn_core_bwd(dM, Wo, A, Gn, sq, temp, *outs):
-                be.attn_bwd_fused(dM, Wo, A, Gn, sq, temp, *outs)
+            assert be.attn_core_bwd(dM, Wo, A, Gn, sq, temp, *outs)
 
     res = [profile(lambda i, f=f: run(i, f)) for f in (False, True)]
     print(f"c={c} heads={heads} C={C} {side}x{side} B={B}  (dM to the row groups: " + (f"{split[-1]} slabs)" if split else "dense)"))
-    for tag, rows in zip(("parent route", "row groups  "), res):
+    for tag, rows in zip(("one launch ", "row groups "), res):
         watched = {k: v for k, v in rows.items() if any(w in k for w in WATCH)}
         other = sum(v for k, v in rows.items() if k not in watched)
         print(f"  {tag}: " + " + ".join(f"{k} {v:.1f}" for k, v in watched.items()) + f" = {sum(watched.values()):.1f} us   (dM product {other:.1f} us)", flush=True)

@@ -348,26 +348,19 @@ class TorchDouble:
         MfT.view(B, hd, c, C).copy_(torch.einsum("bhij,him->bhjm", A, W))
         return True
 
-    @staticmethod
-    def attn_fused_ok(c):
-        return c in (48, 96)
-
     def attn_core_bwd(self, dM, Wo, A, Gn, sq, temp, Mf, dWo_part, dtemp_part, Eq, EqT, Dq, Dk):
-        B, hd, c, _ = A.shape
-        if ((hd * c) % 16) or c not in (24, 48, 96):
-            return False
-        self.attn_bwd_fused(dM, Wo, A, Gn, sq, temp, Mf, dWo_part, dtemp_part, Eq, EqT, Dq, Dk)
-        return True
-
-    def attn_bwd_fused(self, dM, Wo, A, Gn, sq, temp, Mf, dWo_part, dtemp_part, Eq, EqT, Dq, Dk):
+        """same support rule as rcot_attn_core_bwd / rcot_attn_rows_bwd; the specification both are tested against"""
         B, hd, c, _ = A.shape
         C = hd * c
+        if (C % 16) or c not in (24, 48, 96):
+            return False
         Wh = Wo.view(C, hd, c).permute(1, 0, 2).unsqueeze(0)            # [1, hd, C, c]
         Dh = dM.view(B, C, hd, c).permute(0, 2, 1, 3)                    # [B, hd, C, c]
         Mf.view(B, C, hd, c).permute(0, 2, 1, 3).copy_(Wh @ A)
         dWo_part.view(B, C, hd, c).permute(0, 2, 1, 3).copy_(Dh @ A.transpose(-1, -2))
         dA = Wh.transpose(-1, -2) @ Dh
         self.attn_bwd_small(dA.contiguous(), A, Gn, sq, temp, dtemp_part, Eq, EqT, Dq, Dk)
+        return True
 
     def attn_bwd_small(self, dA, A, Gn, sq, temp, dtemp_part, Eq, EqT, Dq, Dk):
         B, hd, c, _ = A.shape

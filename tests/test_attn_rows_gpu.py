@@ -1,6 +1,6 @@
-"""GPU tier: the attention-matrix backward as row groups on many workgroups plus a c x c tail (rcot_attn_rows_bwd) against the fp64
-double of attn_bwd_fused (tests/host_double.py), against the one-launch form (rcot_attn_core_bwd) and, through the block, against
-the route of the parent.  dM is handed over dense and as S = 1, 3, 8 and 11 split-K slabs with a leading dimension above C; every
+"""GPU tier: the attention-matrix backward as row groups on many workgroups plus a c x c tail (rcot_attn_rows_bwd) against its fp64
+double (TorchDouble.attn_core_bwd, tests/host_double.py), against the one-launch form (rcot_attn_core_bwd) and, through the block,
+against the route that takes the one-launch form at every head width.  dM is handed over dense and as S = 1, 3, 8 and 11 split-K slabs with a leading dimension above C; every
 output starts as NaN, the workspace is poisoned, every tensor lies between guard bands.
 """
 import ctypes
@@ -134,9 +134,9 @@ def test_attn_rows_bwd_refuses_what_the_one_launch_form_refuses(hip):
 
 @pytest.mark.parametrize("C,heads", [(96, 1), (96, 2)])
 def test_block_backward_row_group_route_vs_parent_route(hip, C, heads):
-    """TransformerBlockOp.backward at B = 2, 16x16 with the row-group form forced through the wrapper against the route of the
-    parent (one launch at c = 48, row chunks + tail at c = 96): dx and every parameter gradient, to the bars of
-    test_transformer_block_vs_reference_fixture."""
+    """TransformerBlockOp.backward at B = 2, 16x16 with the row-group form forced through the wrapper ("on") against the one-launch
+    form forced the same way ("off", c = 48 and c = 96 alike): dx and every parameter gradient, to the bars of
+    test_transformer_block_vs_reference_fixture.  The profile of each run names the kernel of its route and not the other's."""
     from rcot_amd import params as P
     from rcot_amd.net_restormer import ParamStore, TransformerBlockOp
     be = hip
@@ -157,7 +157,9 @@ def test_block_backward_row_group_route_vs_parent_route(hip, C, heads):
             be.side_join()
             torch.cuda.synchronize()
             assert be.L.rcot_profile_end(buf, 1 << 16) > 10
-            assert ("attn_rows_tail_kernel" in buf.value.decode(errors="replace")) == (route == "on")
+            ran = buf.value.decode(errors="replace")
+            assert ("attn_rows_tail_kernel" in ran) == (route == "on")
+            assert ("attn_bwd_core_kernel" in ran) == (route == "off")
             res[route] = (dx, {n: st.g[n].clone() for n, _ in shapes})
     finally:
         del be.attn_rows

@@ -222,6 +222,32 @@ def test_whole_image_with_odd_latent_plane_matches_oracle(tnet):
     assert relerr(net(x), ref) < 1e-9
 
 
+def test_block_backward_fallback_branch_matches_attn_core_bwd():
+    """TransformerBlockOp.backward where the backend's attn_core_bwd declines (head widths other than 24 / 48 / 96 on the device):
+    the three products one by one and attn_bwd_small give dx and every parameter gradient of the attn_core_bwd branch — the same
+    fp64 arithmetic in another association, hence 1e-12."""
+    from rcot_amd.net_restormer import ParamStore, TransformerBlockOp
+    C, heads = 48, 2
+    shapes = P.block_param_shapes("blk", C, heads)
+    x, gy = seeded_tensor(21, (1, C, 8, 8), dtype=D), seeded_tensor(22, (1, C, 8, 8), dtype=D)
+    be, res = TorchDouble(D), []
+    for decline in (False, True):
+        if decline:
+            be.attn_core_bwd = lambda *a: False
+        st = ParamStore(be, shapes, [n for n, _ in shapes], [])
+        st.load(_params(shapes, 5, "T"))
+        blk = TransformerBlockOp(be, st, "blk", C, heads)
+        blk.repack()
+        _, ctx = blk.forward(x, True)
+        dx = blk.backward(ctx, gy)
+        be.side_join()
+        res.append((dx, {n: st.g[n].clone() for n, _ in shapes}))
+    assert float(res[0][0].abs().max()) > 0
+    assert relerr(res[1][0], res[0][0]) < 1e-12
+    for n, _ in shapes:
+        assert relerr(res[1][1][n], res[0][1][n]) < 1e-12, n
+
+
 def test_grad_reducer_bucket_order_front_and_tail():
     """parallel.GradReducer: ready() releases complete buckets from the front of the flat buffer (critic-loss / generator
     backward), ready_tail() from its end (the gradient penalty's first-to-last sweep); every bucket leaves exactly once, whatever
