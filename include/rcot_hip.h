@@ -25,7 +25,7 @@ extern "C" {
 
 /* Bumped on EVERY signature change; returned by rcot_abi_version() (csrc/api.hip) and compared by the loader
  * (rcot_amd/lib.py ABI_VERSION, tests/test_abi.py) so that a stale prebuilt .so is refused, not mis-called. */
-#define RCOT_ABI_VERSION 36
+#define RCOT_ABI_VERSION 37
 
 /* Arithmetic of the MFMA products of the three GEMM-shaped entry points that take `prec` (rcot_gemm_kmajor,
  * rcot_conv1x1_wgrad, rcot_bmm_nt); operands and results are fp32 in memory either way.
@@ -411,6 +411,15 @@ int rcot_rmsprop_step(float* p, const float* g, float* sq, long n, double lr, do
                       double grad_scale, void* stream);
 int rcot_adam_step(float* p, const float* g, float* m, float* v, long n, double lr, double b1, double b2, double eps,
                    int step, double grad_scale, void* stream);
+/* Exponential moving average of a parameter buffer (weight averaging; rcot_amd/ema.py):
+ *     ema[i] = fmaf(omd, p[i] - ema[i], ema[i]),   omd = (float)(1.0 - decay)   (the subtraction from 1 in double, on the host)
+ * The increment form: p - ema is exact or nearly so where the two are close, so the average stalls only where
+ * |p - ema| < 2^-24 |ema| / omd.  NaN and Inf propagate; p is not written.  One launch, no workspace, 64-bit indices.  Any n >= 1 and any
+ * 4-byte-aligned pointers: 16-byte loads and stores over n / 4 elements plus a tail of up to 3 in the same launch when both pointers are
+ * 16-byte aligned, a scalar grid-stride sweep otherwise.
+ *  RCOT_EINVAL (nothing is launched, ema is untouched): a null pointer; n <= 0; a decay that is NaN or outside [0, 1); a pointer that is
+ *  not 4-byte aligned; [ema, ema + n) and [p, p + n) overlapping. */
+int rcot_ema_step(float* ema, const float* p, long n, double decay, void* stream);
 
 /* ---- the reference's OLDER transport map: MPRNet-style Net.T_net (Net.py:179-216) ----------------------------
  * Its 3x3 / 1x1 convolutions are rcot_conv2d_fwd / _dgrad / _wgrad (KH = KW = 3 or 1, no bias); these are the pieces between them

@@ -46,6 +46,32 @@ __global__ __launch_bounds__(256) void adam_kernel(float4* __restrict__ p, const
         v[i] = vv;
     }
 }
+// Weight average: ema += omd * (p - ema), one fused multiply-add per element (3 streams of 4 B per element).  The increment form keeps
+// p - ema exact (or nearly so) where the two are close, which is what an fp32 average at decay 0.999 rests on.
+// vec: n4 float4 elements grid-stride, then the n - 4 n4 <= 3 tail elements by the first lanes of workgroup 0; else n scalars.
+__device__ __forceinline__ float ema_one(float e, float pv, float omd) { return __builtin_fmaf(omd, pv - e, e); }
+
+__global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ ema, const float* __restrict__ p, long n, float omd, int vec) {
+    const long t0 = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256;
+    if (vec) {
+        float4* __restrict__ e4 = (float4*)ema;
+        const float4* __restrict__ p4 = (const float4*)p;
+        const long n4 = n >> 2;
+        for (long i = t0; i < n4; i += stride) {
+            float4 ev = e4[i];
+            const float4 pv = p4[i];
+            ev.x = ema_one(ev.x, pv.x, omd);
+            ev.y = ema_one(ev.y, pv.y, omd);
+            ev.z = ema_one(ev.z, pv.z, omd);
+            ev.w = ema_one(ev.w, pv.w, omd);
+            e4[i] = ev;
+        }
+        const long i = (n4 << 2) + t0;
+        if (t0 < 3 && i < n) ema[i] = ema_one(ema[i], p[i], omd);
+    } else {
+        for (long i = t0; i < n; i += stride) ema[i] = ema_one(ema[i], p[i], omd);
+    }
+}
 }  // namespace
 
 extern "C" {
@@ -76,6 +102,24 @@ int rcot_adam_step(float* p, const float* g, float* m, float* v, long n, double 
     RCOT_LAUNCH(adam_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, (float4*)p, (const float4*)g,
                        (float4*)m, (float4*)v, n4, (float)lr, (float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2),
                        (float)eps, (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), (float)grad_scale);
+    RCOT_LAUNCH_CHECK();
+    return RCOT_OK;
+}
+
+// 1 - decay is formed in double, as 1 - alpha above.  Any n >= 1 and any 4-byte-aligned pointers: float4 accesses when both are
+// 16-byte aligned, a scalar grid-stride sweep otherwise.  !(0 <= decay < 1) also refuses NaN.
+int rcot_ema_step(float* ema, const float* p, long n, double decay, void* stream) {
+    if (!ema || !p || n <= 0 || !(decay >= 0.0 && decay < 1.0)) return RCOT_EINVAL;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(ema), b = reinterpret_cast<uintptr_t>(p);
+    if ((a & 3) || (b & 3)) return RCOT_EINVAL;
+    const uintptr_t bytes = (uintptr_t)n * 4;
+    if (a < b + bytes && b < a + bytes) return RCOT_EINVAL;              // the ranges overlap
+    const int vec = al16(ema) && al16(p);
+    const long items = vec ? (n >> 2) : n;
+    long grid = (items + 255) / 256;
+    if (grid > 4096) grid = 4096;
+    if (grid < 1) grid = 1;                                             // n < 4 on the float4 path: the tail alone
+    RCOT_LAUNCH(ema_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, ema, p, n, (float)(1.0 - decay), vec);
     RCOT_LAUNCH_CHECK();
     return RCOT_OK;
 }

@@ -9,7 +9,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 36     # == RCOT_ABI_VERSION in include/rcot_hip.h (checked by tests/test_abi.py and at load time)
+ABI_VERSION = 37    # == RCOT_ABI_VERSION in include/rcot_hip.h (checked by tests/test_abi.py and at load time)
 PREC_FP32, PREC_BF16X3, PREC_BF16X6, PREC_BF16X1 = 0, 1, 2, 3     # RCOT_PREC_* of include/rcot_hip.h
 LIB_PATH = os.environ.get("RCOT_LIB") or os.path.join(_HERE, "librcot_hip.so")   # RCOT_LIB: A/B builds while tuning
 
@@ -106,6 +106,7 @@ SIGNATURES = {
     "rcot_patch_prep_batch": [_f, _i, _i, _f, _f, _f],                                         # table: a DEVICE int64 array
     "rcot_rmsprop_step": [_f, _f, _f, _l, _d, _d, _d, _d, _f],
     "rcot_adam_step": [_f, _f, _f, _f, _l, _d, _d, _d, _d, _i, _d, _f],
+    "rcot_ema_step": [_f, _f, _l, _d, _f],
     # the MPRNet backbone's pointwise pieces (csrc/mprnet_ops.hip)
     "rcot_prelu_fwd": [_f, _f, _f, _l, _f],
     "rcot_prelu_bwd": [_f, _f, _f, _f, _f, _l, _f, _sz, _f],

@@ -1616,3 +1616,7 @@ class HipBackend:
     def adam_step(self, p, g, m, v, n, lr, step, b1=0.9, b2=0.999, eps=1e-8, grad_scale=1.0):
         _lib.check(self.L.rcot_adam_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, lr, b1, b2, eps,
                                          step, grad_scale, self._st()), "rcot_adam_step")
+
+    def ema_step(self, ema, p, n, decay):
+        """ema[0:n) += (1 - decay) (p[0:n) - ema[0:n)) in one launch (rcot_amd/ema.py); any n >= 1, any fp32 alignment"""
+        _lib.check(self.L.rcot_ema_step(ema.data_ptr(), p.data_ptr(), n, decay, self._st()), "rcot_ema_step")

@@ -237,6 +237,8 @@ class PlannedMinimax:
         out = [st.T.store.flat, st.F.store.flat]
         for o in (st.To, st.Fo):
             out += list(o._state_tensors().values())
+        if st.ema is not None:                   # the warm-up pass must not leave a phantom update in the weight average either
+            out.append(st.ema.buf)
         return out
 
     def _key(self, degraded, paired):
@@ -297,10 +299,13 @@ class PlannedMinimax:
             # fp32 plan, then the first bf16x3 iteration recorded without a warm-up).  The pass must not count as a training
             # iteration: parameters and optimizer state are put back.
             saved = [t.clone() for t in self._state_tensors()]
+            ema_updates = st.ema.updates if st.ema is not None else 0
             for _ in range(self.warmup):
                 st.iteration(degraded, target, de_id, alpha, paired)
             for t, s_ in zip(self._state_tensors(), saved):
                 t.copy_(s_)
+            if st.ema is not None:
+                st.ema.updates = ema_updates     # (a host-side counter: put back with the buffer)
             del saved
             for net in (st.T, st.F):
                 if hasattr(net, "repack"):
@@ -352,6 +357,8 @@ class PlannedMinimax:
         ent["d"].copy_(de_id, non_blocking=True)
         ent["a"].copy_(alpha, non_blocking=True)
         ent["plan"].replay()
+        if st.ema is not None:
+            st.ema.updates += 1                  # the replayed rcot_ema_step launch (the decay is a constant by-value argument)
         st.logs = ent["logs"]
         return ent["out"]
 

@@ -70,6 +70,9 @@ file's index in the sorted ``--tarset`` listing (``chain.file_draws``), so a tab
 bytes ``python -m rcot_amd.chain`` writes for the same seed (after the degradation ``--pad none`` still crops both images to a multiple
 of 4, as for every task; the folder tool does not).  It is refused together with ``--sr_scale``, ``--jpeg_q``, ``--blur`` or
 ``--noise_sigma``.
+
+Superset: ``--weights ema`` restores with the averaged weights that ``rcot_amd.trainer --ema`` saves under "Tnet_ema" (either backbone); it
+exits with a message naming the key when the checkpoint has none.  The default ``raw`` reads "Tnet" as before.
 """
 from __future__ import annotations
 
@@ -134,6 +137,9 @@ parser.add_argument("--chain", default=None, type=str,
                     help="superset: a degradation chain: the network's input is the target after these stages made on the device "
                          "(rcot_amd/chain.py: blur_g1.6+noise_g10+jpeg_q40; --degset is not read; --seed seeds the per-file values); off by "
                          "default, everything as before")
+parser.add_argument("--weights", choices=["raw", "ema"], default="raw",
+                    help="superset: ema = the averaged weights of a checkpoint written with rcot_amd.trainer --ema (its \"Tnet_ema\" key); "
+                         "raw = \"Tnet\", everything as before")
 parser.add_argument("--savedeg", default=None, type=str, help="superset: also write the 8-bit network input (with --sr_scale: the bicubic "
                                                              "baseline) as PNGs under this folder")
 
@@ -196,10 +202,16 @@ def evaluate_folders(path1: str, path2: str, ssim_window: str = "box2", color: s
 
 
 # ------------------------------------------------------------------------------- the network of a checkpoint
-def load_network(path: str):
-    """-> (callable network on the GPU, multiple its input sizes must have)"""
+def load_network(path: str, weights: str = "raw"):
+    """-> (callable network on the GPU, multiple its input sizes must have).  ``weights`` "ema": the averaged weights a run with
+    ``rcot_amd.trainer --ema`` saved under "Tnet_ema" (a plain state_dict, either backbone) instead of "Tnet"."""
     from .compat import load_checkpoint
     ck = load_checkpoint(path)
+    if weights == "ema":
+        if not isinstance(ck, dict) or "Tnet_ema" not in ck:
+            raise SystemExit(f"--weights ema: {path} has no \"Tnet_ema\" key (it was not written by rcot_amd.trainer --ema); "
+                             f"--weights raw reads \"Tnet\"")
+        ck = dict(ck, Tnet=dict(ck["Tnet_ema"]))
     if isinstance(ck, dict) and ck.get("backbone") == "mprnet":
         from .mprnet_hip import MPRNetHip
         net = MPRNetHip(seed=0)
@@ -401,7 +413,7 @@ def main(argv=None):
         raise SystemExit(f"--sr_scale {opt.sr_scale}: the scale factor must be an integer >= 2 (0 = off)")
     for d in (opt.save, opt.savetar, opt.saveres) + ((opt.savedeg,) if opt.savedeg else ()):
         os.makedirs(d, exist_ok=True)
-    net, mult = load_network(opt.model)
+    net, mult = load_network(opt.model, opt.weights)
     if opt.pad != "none" or opt.metrics == "device" or opt.sr_scale > 0 or opt.jpeg_q > 0 or opt.blur is not None or opt.chain is not None:
         return _main_any_size(opt, net)
     deg_list, tar_list = sorted(glob.glob(opt.degset + "*")), sorted(glob.glob(opt.tarset + "*"))

@@ -4,7 +4,8 @@ Keeps the reference's CLI flags (trainer.py:22-58), learning-rate schedule (:228
 structure (critic step -> separate gradient-penalty step -> generator step, :262-346), print format
 (:348-354) and checkpoint naming/keys (:362-371).  The compute is done by ``rcot_amd.net_restormer``
 (HIP kernels); this file only sequences it.  Additions are supersets: ``--seed``, ``--synthetic``,
-``--iters``, data-parallel launch through torchrun (one process per GPU, RCCL).
+``--iters``, data-parallel launch through torchrun (one process per GPU, RCCL), ``--ema`` / ``--val_weights`` (an exponential
+moving average of the transport map's weights: validated, saved next to the raw weights; rcot_amd/ema.py).
 """
 from __future__ import annotations
 
@@ -87,6 +88,14 @@ parser.add_argument("--data_cache", choices=["off", "device"], default="off",
 parser.add_argument("--data_cache_gb", type=float, default=16.0,
                     help="--data_cache device: budget of image bytes per rank, in GiB; an image that does not fit is decoded again "
                          "whenever a batch needs it (no eviction: what is resident depends only on the order of first touches)")
+parser.add_argument("--ema", type=float, default=0.0,
+                    help="weight averaging: keep an exponential moving average of the transport map's weights with this decay, 0 < D < 1 "
+                         "(0.999 is usual), updated once per iteration by one launch (rcot_amd/ema.py); it is validated (--val_weights), "
+                         "saved under \"Tnet_ema\" next to the raw weights and read by rcot_amd.tester --weights ema.  0 = off, everything "
+                         "as before")
+parser.add_argument("--val_weights", choices=["ema", "raw", "both"], default=None,
+                    help="with --ema: the weights the per-epoch validation runs on (default ema); both writes psnr (the average) and "
+                         "psnr_raw")
 parser.add_argument("--synthetic", action="store_true", help="seeded synthetic patches (no dataset folders needed)")
 parser.add_argument("--iters", type=int, default=20, help="iterations per epoch with --synthetic")
 
@@ -110,6 +119,24 @@ def check_degradation_flags(o) -> None:
         degrade.folder(task, o, tasks[0][0])
         for read in task.options:
             read(o)
+
+
+def check_ema_flags(o, stock_mprnet: bool = False) -> None:
+    """--ema D needs 0 < D < 1 (0, the default, is off) and a network with a flat parameter store (not the stock-ops MPRNet loop);
+    --val_weights needs --ema.  Sets the default of --val_weights.  Refused up front with SystemExit naming the flag."""
+    if o.ema != 0.0:
+        from .ema import check_decay
+        try:
+            check_decay(o.ema)
+        except ValueError:
+            raise SystemExit(f"--ema {o.ema}: the decay must satisfy 0 < D < 1 (0.999 is usual; 0 = off)")
+        if stock_mprnet:
+            raise SystemExit("--ema needs a network with a flat parameter store: --backbone mprnet on stock PyTorch ops (no GPU visible, or "
+                             "RCOT_MPRNET_STOCK=1) has none")
+        if o.val_weights is None:
+            o.val_weights = "ema"
+    elif o.val_weights is not None:
+        raise SystemExit(f"--val_weights {o.val_weights} chooses between the raw weights and their average: it needs --ema D")
 
 
 def check_patch_size(P: int) -> int:
@@ -238,8 +265,11 @@ class MinimaxStep:
     """The body of the reference's training loop (trainer.py:247-346) for one (local) batch."""
 
     def __init__(self, Tnet: T_net, Fnet: F_net, T_opt: FlatOptimizer, F_opt: FlatOptimizer, sigma: float,
-                 Sigma: float, bucket_elems: int = 8 << 20):
+                 Sigma: float, bucket_elems: int = 8 << 20, ema=None):
         self.T, self.F, self.To, self.Fo = Tnet, Fnet, T_opt, F_opt
+        #: optional rcot_amd.ema.WeightAverage of the transport map: one update per iteration, right after its optimizer step (the
+        #: potential is not averaged: it is never used at inference)
+        self.ema = ema
         self.sigma, self.Sigma = float(sigma), float(Sigma)
         self.be = Tnet.be
         self.world = par.world_size()
@@ -331,6 +361,8 @@ class MinimaxStep:
         if self.grad_probe is not None:
             self.grad_probe("T_gen")
         self.To.step()                                               # :346
+        if self.ema is not None:
+            self.ema.update()                                        # on the weights this iteration produced; recorded into the plan like any launch
         self.logs = dict(f_out=f_out, fo=fo, scal=scal, gp=gp, B=B, Bg=Bg, paired=paired)
         return out
 
@@ -460,11 +492,13 @@ def _as_picklable(net, cls):
     return C.from_state_dict(net.state_dict(), **kw)
 
 
-def save_checkpoint(Tnet, Fnet, epoch, T_optimizer=None, F_optimizer=None):
+def save_checkpoint(Tnet, Fnet, epoch, T_optimizer=None, F_optimizer=None, ema=None):
     """trainer.py:362-371: same path pattern and dict keys, and — like the reference — whole network OBJECTS under
     "Tnet"/"Fnet" (class paths ``Net_Restormer.T_net`` / ``F_net``; see rcot_amd/compat.py), so that
     ``torch.load(p)["Tnet"]`` can be called (tester.py:54) and ``.state_dict()`` read (trainer.py:105).  Superset:
-    optimizer state under "T_optimizer"/"F_optimizer" (the reference loses RMSprop's square_avg on resume)."""
+    optimizer state under "T_optimizer"/"F_optimizer" (the reference loses RMSprop's square_avg on resume); with ``ema`` (a
+    WeightAverage of Tnet) the averaged weights as a plain state_dict under "Tnet_ema" and {"decay", "updates"} under "ema" —
+    "Tnet" stays the raw network, which a resumed run keeps training."""
     path = "checkpoint/" + "model_" + str(opt.type) + "_" + "_" + str(opt.nEpochs) + "_" + str(opt.sigma) + ".pth"
     os.makedirs("checkpoint/", exist_ok=True)
     if not hasattr(Tnet, "decoder"):
@@ -477,6 +511,9 @@ def save_checkpoint(Tnet, Fnet, epoch, T_optimizer=None, F_optimizer=None):
     for key, o in (("T_optimizer", T_optimizer), ("F_optimizer", F_optimizer)):
         if o is not None:
             state[key] = o.state_dict()
+    if ema is not None:
+        state["Tnet_ema"] = ema.tensors()
+        state["ema"] = {"decay": ema.decay, "updates": ema.updates}
     torch.save(state, path)
     print("Checkpoint saved to {}".format(path))
     return path
@@ -666,6 +703,7 @@ def main(argv=None):
     # --backbone mprnet: with a GPU the older transport map runs on the HIP kernels (rcot_amd/mprnet_hip.py) through everything below —
     # data folders, data parallelism, validation, launch plans; without one (or with RCOT_MPRNET_STOCK=1) the stock-ops loop
     hip_mprnet = opt.backbone == "mprnet" and torch.cuda.is_available() and os.environ.get("RCOT_MPRNET_STOCK", "0") != "1"
+    check_ema_flags(opt, stock_mprnet=opt.backbone == "mprnet" and not hip_mprnet)
     if opt.backbone == "mprnet" and not hip_mprnet:
         return main_mprnet()
     if "RANK" in os.environ and "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) > 1:
@@ -702,6 +740,7 @@ def main(argv=None):
     Fnet = _make_net("F_net", patch_size=opt.patch_size, seed=seed + 1)    # :93
     T_opt, F_opt = make_optimizers(Tnet, Fnet, opt.optimizer, opt.lr)
     from .compat import load_checkpoint
+    ck = None
     if opt.resume:
         if os.path.isfile(opt.resume):
             ck = load_checkpoint(opt.resume)
@@ -729,6 +768,22 @@ def main(argv=None):
             net.repack()
     for o in (T_opt, F_opt):
         o.broadcast_state()
+    # the weight average of the transport map (--ema): made from the weights as loaded and broadcast, then continued from the
+    # checkpoint's own average when it has one
+    avg = None
+    has_avg = isinstance(ck, dict) and "Tnet_ema" in ck
+    if opt.ema:
+        from .ema import WeightAverage
+        avg = WeightAverage(Tnet, opt.ema)
+        if has_avg:
+            avg.load_state_dict(dict(ck["Tnet_ema"]))
+            avg.updates = int((ck.get("ema") or {}).get("updates", 0))
+        elif ck is not None and rank == 0:
+            print(f"=> '{opt.resume}' holds no weight average (\"Tnet_ema\"): the average starts from the loaded weights")
+        avg.broadcast()
+    elif has_avg and rank == 0:
+        print(f"=> '{opt.resume}' holds a weight average (\"Tnet_ema\"): ignored without --ema")
+    ck = None
     if opt.synthetic:
         from .synth import SyntheticLoader
         loader = SyntheticLoader(opt.de_type, opt.batchSize // world, opt.patch_size, opt.iters, seed=seed, rank=rank,
@@ -742,7 +797,7 @@ def main(argv=None):
         loader = FolderLoader(opt, opt.batchSize // world, seed=seed, rank=rank, world=world, threads=opt.threads, cache=cache)
     import glob
     deg_list, tar_list = sorted(glob.glob(opt.degset + "*")), sorted(glob.glob(opt.tarset + "*"))   # :137-141
-    stepper = MinimaxStep(Tnet, Fnet, T_opt, F_opt, opt.sigma, opt.Sigma)
+    stepper = MinimaxStep(Tnet, Fnet, T_opt, F_opt, opt.sigma, opt.Sigma, ema=avg)
     stepper.sample_dir = "./checksample/" + str(opt.type) + "/" if rank == 0 else None
     TLOSS, PLOSS = [], []
     for epoch in range(opt.start_epoch, opt.nEpochs + 1):
@@ -754,10 +809,18 @@ def main(argv=None):
             print(f"epoch {epoch}: {len(loader) * opt.batchSize / dt:.1f} patches/s")
             if getattr(loader, "cache", None) is not None:
                 print(loader.cache.report())
-            p = evaluate(Tnet, deg_list, tar_list, pad=opt.val_pad)        # :149
+            extra = ""
+            if avg is None or opt.val_weights == "raw":
+                p = evaluate(Tnet, deg_list, tar_list, pad=opt.val_pad)    # :149
+            else:                                                          # --ema: on the averaged weights, the raw ones back afterwards
+                if opt.val_weights == "both":
+                    extra = f", psnr_raw {evaluate(Tnet, deg_list, tar_list, pad=opt.val_pad):.4f}"
+                with avg.applied():
+                    p = evaluate(Tnet, deg_list, tar_list, pad=opt.val_pad)
+            suffix = "" if avg is None else ", weights " + ("raw" if opt.val_weights == "raw" else f"ema{opt.ema:g}")
             os.makedirs("./checksample/" + str(opt.type), exist_ok=True)
             with open("./checksample/" + str(opt.type) + "/validation_results.txt", "a") as f:      # :151-153
-                f.write(f"Patchsize {opt.patch_size} Epoch {epoch}, psnr {p:.4f}, Batchsize {opt.batchSize}\n")
+                f.write(f"Patchsize {opt.patch_size} Epoch {epoch}, psnr {p:.4f}{extra}, Batchsize {opt.batchSize}{suffix}\n")
             TLOSS.append(format(b / 2))                                    # :157-162 (len(data_list) == 2)
             PLOSS.append(format(c / 2))
             try:
@@ -766,7 +829,7 @@ def main(argv=None):
                 scio.savemat('PLOSSrain.mat', {'PLOSS': PLOSS})
             except ImportError:
                 pass
-            save_checkpoint(Tnet, Fnet, epoch, T_opt, F_opt)               # :165 (mprnet backbone: the state_dict form)
+            save_checkpoint(Tnet, Fnet, epoch, T_opt, F_opt, avg)          # :165 (mprnet backbone: the state_dict form)
         if world > 1:
             torch.distributed.barrier()
     return Tnet, Fnet
