@@ -25,7 +25,7 @@ extern "C" {
 
 /* Bumped on EVERY signature change; returned by rcot_abi_version() (csrc/api.hip) and compared by the loader
  * (rcot_amd/lib.py ABI_VERSION, tests/test_abi.py) so that a stale prebuilt .so is refused, not mis-called. */
-#define RCOT_ABI_VERSION 37
+#define RCOT_ABI_VERSION 38
 
 /* Arithmetic of the MFMA products of the three GEMM-shaped entry points that take `prec` (rcot_gemm_kmajor,
  * rcot_conv1x1_wgrad, rcot_bmm_nt); operands and results are fp32 in memory either way.
@@ -420,6 +420,69 @@ int rcot_adam_step(float* p, const float* g, float* m, float* v, long n, double 
  *  RCOT_EINVAL (nothing is launched, ema is untouched): a null pointer; n <= 0; a decay that is NaN or outside [0, 1); a pointer that is
  *  not 4-byte aligned; [ema, ema + n) and [p, p + n) overlapping. */
 int rcot_ema_step(float* ema, const float* p, long n, double decay, void* stream);
+
+/* ---- gradient-norm clipping and non-finite step skip, decided on the device (rcot_amd/trainer.py FlatOptimizer(max_norm=...)) ----
+ * A guarded optimizer step is three launches on one stream, with no host read between them:
+ *     rcot_grad_sumsq  ->  rcot_grad_decide  ->  rcot_rmsprop_step_guarded | rcot_adam_step_guarded (once per range)
+ * They communicate through two device buffers of the caller: a workspace of RCOT_SUMSQ_MAX_PARTS doubles and the CONTROL BLOCK, one per
+ * optimizer: RCOT_CB_WORDS 8-byte words, doubles (D) and 64-bit integers (I), 8-byte aligned, zero-filled by the caller before first use:
+ *     word  0  D  lr         learning rate; written by the HOST only (a stream-ordered write between launches), read by the step kernels
+ *     word  1  D  max_norm   the cap on the gradient norm, +inf = guard only; written by the host only
+ *     word  2  D  norm       sqrt(sum g^2) of the last decision (Inf or NaN when it skipped)
+ *     word  3  D  scale      min(1, max_norm / (norm + 1e-6)) of the last decision (torch.nn.utils.clip_grad_norm_); 0 when it skipped
+ *     word  4  I  steps      decisions made
+ *     word  5  I  clipped    decisions with scale < 1
+ *     word  6  I  skipped    decisions that found a non-finite sum
+ *     word  7  D  max_seen   the largest finite norm seen
+ *     word  8  I  skip       1 when the last decision skipped, else 0: what the guarded step launches read (and a decision with RCOT_DECIDE_INHERIT)
+ *     words 9, 10   I  t[0], t[1]      Adam step counts (FlatOptimizer's t_main, t_tail)
+ *     words 11, 12  D  bc1[0], bc1[1]  1 - beta1^t[k], formed by the decision that advanced t[k]
+ *     words 13, 14  D  bc2[0], bc2[1]  1 - beta2^t[k]
+ *     word  15      reserved
+ * Everything but lr and max_norm is written by rcot_grad_decide alone (one workgroup).
+ *
+ * rcot_grad_sumsq: partials[b] = the fp64 sum of the squares of workgroup b's share of g[0:n), b < rcot_grad_sumsq_parts(n) (a host
+ *   function of n alone: min(4096, max(1, ceil((n / 4) / 256)))).  One pass, 16-byte loads; any n >= 1 and any 4-byte-aligned g (the
+ *   elements before the first 16-byte boundary and the tail of n % 4 are added by the first lanes of workgroup 0).  Every square is exact
+ *   in fp64, so the total is within n 2^-53 relative of the exact sum in any order, and it is non-finite exactly when an element is.
+ *   Plain stores, one per workgroup; no atomics.  g is not written.
+ * rcot_grad_decide: ONE workgroup sums partials[0:nparts) in a fixed order and applies the rule above: norm, scale, skip = !isfinite(sum),
+ *   the counters.  flags: RCOT_DECIDE_ADAM0 / _ADAM1 (bit k = 0, 1): t[k] += 1 and bc1[k], bc2[k] from b1, b2 — only when the step is not
+ *   skipped; neither for RMSprop.  RCOT_DECIDE_INHERIT: this step uses the same batch as the step the block decided last (the gradient-
+ *   penalty step after the critic step: both read the target images), so when block.skip is still set from that decision this one skips as
+ *   well, whatever its own sum, and counts as skipped; norm is still that of its own gradients.  Why: a non-finite input need not reach the
+ *   gradients of every step it spoils — the penalty's gradients of a piecewise linear network are products of weights and activation MASKS,
+ *   a NaN input only picks mask branches and leaves them finite and meaningless.
+ * rcot_rmsprop_step_guarded / rcot_adam_step_guarded: rcot_rmsprop_step / rcot_adam_step (the same per-element expressions) with
+ *   lr = block.lr, grad_scale = block.scale and, for Adam, the bias corrections of counter `counter`: step_size = (float)(lr / bc1),
+ *   (float)(1 / sqrt(bc2)), formed in double as rcot_adam_step forms them on the host.  When block.skip is set (or the Adam counter is still
+ *   0) the kernel returns before it loads anything: p and the state keep their bits.
+ *  RCOT_EINVAL (nothing is launched): what rcot_rmsprop_step / rcot_adam_step refuse (null, n <= 0, n % 4, 16-byte alignment); for
+ *  rcot_grad_sumsq a null pointer, n <= 0, g not 4-byte or partials not 8-byte aligned; a block or workspace that is not 8-byte aligned;
+ *  nparts outside 1 .. RCOT_SUMSQ_MAX_PARTS; flags outside 0 .. 7; counter outside 0 .. 1. */
+#define RCOT_SUMSQ_MAX_PARTS 4096
+#define RCOT_DECIDE_ADAM0 1
+#define RCOT_DECIDE_ADAM1 2
+#define RCOT_DECIDE_INHERIT 4
+#define RCOT_CB_WORDS 16
+#define RCOT_CB_LR 0
+#define RCOT_CB_MAX_NORM 1
+#define RCOT_CB_NORM 2
+#define RCOT_CB_SCALE 3
+#define RCOT_CB_STEPS 4
+#define RCOT_CB_CLIPPED 5
+#define RCOT_CB_SKIPPED 6
+#define RCOT_CB_MAX_SEEN 7
+#define RCOT_CB_SKIP 8
+#define RCOT_CB_T 9
+#define RCOT_CB_BC1 11
+#define RCOT_CB_BC2 13
+int rcot_grad_sumsq_parts(long n);                     /* returns the count (no launch) */
+int rcot_grad_sumsq(const float* g, long n, double* partials, void* stream);
+int rcot_grad_decide(const double* partials, int nparts, double* ctrl, int flags, double b1, double b2, void* stream);
+int rcot_rmsprop_step_guarded(float* p, const float* g, float* sq, long n, double alpha, double eps, const double* ctrl, void* stream);
+int rcot_adam_step_guarded(float* p, const float* g, float* m, float* v, long n, double b1, double b2, double eps, const double* ctrl,
+                           int counter, void* stream);
 
 /* ---- the reference's OLDER transport map: MPRNet-style Net.T_net (Net.py:179-216) ----------------------------
  * Its 3x3 / 1x1 convolutions are rcot_conv2d_fwd / _dgrad / _wgrad (KH = KW = 3 or 1, no bias); these are the pieces between them

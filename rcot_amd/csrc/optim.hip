@@ -8,19 +8,28 @@ namespace {
 
 using rcot::al16;
 
-__global__ __launch_bounds__(256) void rmsprop_kernel(float4* __restrict__ p, const float4* __restrict__ g,
-                                                      float4* __restrict__ sq, long n4, float lr, float alpha, float oma,
-                                                      float eps, float gscale) {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-        float4 pv = p[i], gv = g[i], sv = sq[i];
+// The per-element updates, shared by the plain and the guarded kernels below (one expression each, so that a guarded step with
+// scale 1 is the same arithmetic as the plain one).  They read gv, gscale and the hyper-parameters of the enclosing kernel.
 #define RCOT_RMS(c)                                        \
     {                                                      \
         const float gg = gv.c * gscale;                    \
         sv.c = alpha * sv.c + oma * gg * gg;     \
         pv.c -= lr * gg / (sqrtf(sv.c) + eps);             \
     }
+#define RCOT_ADAM(c)                                                     \
+    {                                                                    \
+        const float gg = gv.c * gscale;                                  \
+        mv.c = b1 * mv.c + omb1 * gg;                              \
+        vv.c = b2 * vv.c + omb2 * gg * gg;                         \
+        pv.c -= step_size * mv.c / (sqrtf(vv.c) * rsqrt_bc2 + eps);     \
+    }
+
+__global__ __launch_bounds__(256) void rmsprop_kernel(float4* __restrict__ p, const float4* __restrict__ g,
+                                                      float4* __restrict__ sq, long n4, float lr, float alpha, float oma,
+                                                      float eps, float gscale) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        float4 pv = p[i], gv = g[i], sv = sq[i];
         RCOT_RMS(x) RCOT_RMS(y) RCOT_RMS(z) RCOT_RMS(w)
-#undef RCOT_RMS
         p[i] = pv;
         sq[i] = sv;
     }
@@ -32,15 +41,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float4* __restrict__ p, const
                                                    float gscale) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
         float4 pv = p[i], gv = g[i], mv = m[i], vv = v[i];
-#define RCOT_ADAM(c)                                                     \
-    {                                                                    \
-        const float gg = gv.c * gscale;                                  \
-        mv.c = b1 * mv.c + omb1 * gg;                              \
-        vv.c = b2 * vv.c + omb2 * gg * gg;                         \
-        pv.c -= step_size * mv.c / (sqrtf(vv.c) * rsqrt_bc2 + eps);     \
-    }
         RCOT_ADAM(x) RCOT_ADAM(y) RCOT_ADAM(z) RCOT_ADAM(w)
-#undef RCOT_ADAM
         p[i] = pv;
         m[i] = mv;
         v[i] = vv;
@@ -71,6 +72,134 @@ __global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ ema, const
     } else {
         for (long i = t0; i < n; i += stride) ema[i] = ema_one(ema[i], p[i], omd);
     }
+}
+
+// ---- gradient-norm clipping and non-finite step skip, decided on the device (control block: include/rcot_hip.h, RCOT_CB_*) ----
+// Three launches per guarded step: sumsq_kernel (one read of the gradients, 4 B per element: one fp64 partial per workgroup), decide_kernel
+// (ONE workgroup: the partials in a fixed order, the rule, the counters) and a guarded step kernel that reads the decision.  Every word a
+// kernel reads was written by an EARLIER launch or by the host: no workgroup reads what another workgroup of its launch writes.
+__device__ __forceinline__ double sq4(double a, const float4 v) {
+    a = fma((double)v.x, (double)v.x, a);
+    a = fma((double)v.y, (double)v.y, a);
+    a = fma((double)v.z, (double)v.z, a);
+    return fma((double)v.w, (double)v.w, a);
+}
+
+// head: the 0 .. 3 elements before the first 16-byte boundary of g (host-computed; <= n).  Then n4 float4 elements grid-stride, four
+// independent loads in flight per lane, then the tail; head and tail (at most 3 + 3 elements) by the first six lanes of workgroup 0.
+// fp64 throughout: the square of an fp32 value is exact in fp64 and the kernel is bound by HBM.
+__global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g, long n, int head, double* __restrict__ partials) {
+    __shared__ double red[4];
+    const long t0 = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256;
+    const float4* __restrict__ g4 = (const float4*)(g + head);
+    const long n4 = (n - head) >> 2;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    long i = t0;
+    for (; i + 3 * stride < n4; i += 4 * stride) {
+        const float4 v0 = g4[i], v1 = g4[i + stride], v2 = g4[i + 2 * stride], v3 = g4[i + 3 * stride];
+        a0 = sq4(a0, v0);
+        a1 = sq4(a1, v1);
+        a2 = sq4(a2, v2);
+        a3 = sq4(a3, v3);
+    }
+    for (; i < n4; i += stride) a0 = sq4(a0, g4[i]);
+    if (t0 < 6) {
+        const long j = t0 < 3 ? t0 : (long)head + (n4 << 2) + (t0 - 3);
+        if (t0 < 3 ? t0 < head : j < n) {
+            const double x = (double)g[j];
+            a1 = fma(x, x, a1);
+        }
+    }
+    double s = (a0 + a1) + (a2 + a3);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// One workgroup.  total = the partials in a fixed order (strided per-thread sums, then a tree); norm, scale and skip by the rule of
+// torch.nn.utils.clip_grad_norm_ / GradScaler; counters; for Adam the step counts named by flags (bit k = RCOT_DECIDE_ADAM0 << k: counter k) advance when the
+// step is taken, and their bias corrections 1 - beta^t are left in the block for the guarded step launches.
+__global__ __launch_bounds__(256) void decide_kernel(const double* __restrict__ partials, int nparts, double* __restrict__ ctrl, int flags,
+                                                     double b1, double b2) {
+    __shared__ double sd[256];
+    const int t = threadIdx.x;
+    double s = 0.0;
+    for (int b = t; b < nparts; b += 256) s += partials[b];
+    sd[t] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) sd[t] += sd[t + o];
+        __syncthreads();
+    }
+    if (t != 0) return;
+    long long* ci = reinterpret_cast<long long*>(ctrl);
+    const double total = sd[0];
+    // RCOT_DECIDE_INHERIT: a later step on the same batch (the gradient penalty after the critic step).  When the block's previous decision
+    // skipped, this one skips too, whatever its own sum: the flag read here was written by an earlier launch.
+    const bool inherited = (flags & RCOT_DECIDE_INHERIT) && ci[RCOT_CB_SKIP] != 0;
+    const bool skip = inherited || !isfinite(total);
+    const double norm = sqrt(total);
+    const double scale = skip ? 0.0 : fmin(1.0, ctrl[RCOT_CB_MAX_NORM] / (norm + 1e-6));
+    ctrl[RCOT_CB_NORM] = norm;
+    ctrl[RCOT_CB_SCALE] = scale;
+    ci[RCOT_CB_SKIP] = skip ? 1 : 0;
+    ci[RCOT_CB_STEPS] += 1;
+    if (skip) {
+        ci[RCOT_CB_SKIPPED] += 1;
+        return;
+    }
+    if (scale < 1.0) ci[RCOT_CB_CLIPPED] += 1;
+    if (norm > ctrl[RCOT_CB_MAX_SEEN]) ctrl[RCOT_CB_MAX_SEEN] = norm;
+    for (int k = 0; k < 2; ++k) {
+        if (!(flags >> k & 1)) continue;
+        const long long tk = ci[RCOT_CB_T + k] + 1;
+        ci[RCOT_CB_T + k] = tk;
+        ctrl[RCOT_CB_BC1 + k] = 1.0 - pow(b1, (double)tk);
+        ctrl[RCOT_CB_BC2 + k] = 1.0 - pow(b2, (double)tk);
+    }
+}
+
+// The plain kernels with the learning rate, the scale and the skip flag read from the control block (uniform loads of words that the
+// decision launch wrote).  A skipped step returns before it loads anything: p and the state stay bit for bit what they were.
+__global__ __launch_bounds__(256) void rmsprop_guarded_kernel(float4* __restrict__ p, const float4* __restrict__ g,
+                                                              float4* __restrict__ sq, long n4, float alpha, float oma, float eps,
+                                                              const double* __restrict__ ctrl) {
+    if (reinterpret_cast<const long long*>(ctrl)[RCOT_CB_SKIP]) return;
+    const float lr = (float)ctrl[RCOT_CB_LR], gscale = (float)ctrl[RCOT_CB_SCALE];
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        float4 pv = p[i], gv = g[i], sv = sq[i];
+        RCOT_RMS(x) RCOT_RMS(y) RCOT_RMS(z) RCOT_RMS(w)
+        p[i] = pv;
+        sq[i] = sv;
+    }
+}
+
+// counter: which of the block's two Adam step counts this range follows.  A count of 0 (no taken decision has advanced it) has no bias
+// correction: the launch does nothing.
+__global__ __launch_bounds__(256) void adam_guarded_kernel(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ m,
+                                                           float4* __restrict__ v, long n4, float b1, float b2, float omb1, float omb2,
+                                                           float eps, const double* __restrict__ ctrl, int counter) {
+    const long long* ci = reinterpret_cast<const long long*>(ctrl);
+    if (ci[RCOT_CB_SKIP] || ci[RCOT_CB_T + counter] <= 0) return;
+    const float step_size = (float)(ctrl[RCOT_CB_LR] / ctrl[RCOT_CB_BC1 + counter]);
+    const float rsqrt_bc2 = (float)(1.0 / sqrt(ctrl[RCOT_CB_BC2 + counter]));
+    const float gscale = (float)ctrl[RCOT_CB_SCALE];
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        float4 pv = p[i], gv = g[i], mv = m[i], vv = v[i];
+        RCOT_ADAM(x) RCOT_ADAM(y) RCOT_ADAM(z) RCOT_ADAM(w)
+        p[i] = pv;
+        m[i] = mv;
+        v[i] = vv;
+    }
+}
+#undef RCOT_RMS
+#undef RCOT_ADAM
+
+inline long step_grid(long n4) {
+    long grid = (n4 + 255) / 256;
+    return grid > 4096 ? 4096 : grid;
 }
 }  // namespace
 
@@ -120,6 +249,53 @@ int rcot_ema_step(float* ema, const float* p, long n, double decay, void* stream
     if (grid > 4096) grid = 4096;
     if (grid < 1) grid = 1;                                             // n < 4 on the float4 path: the tail alone
     RCOT_LAUNCH(ema_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, ema, p, n, (float)(1.0 - decay), vec);
+    RCOT_LAUNCH_CHECK();
+    return RCOT_OK;
+}
+
+// ---- the guarded step (rcot_hip.h): rcot_grad_sumsq -> rcot_grad_decide -> rcot_rmsprop_step_guarded | rcot_adam_step_guarded
+int rcot_grad_sumsq_parts(long n) {
+    if (n <= 0) return 0;
+    const long g = ((n >> 2) + 255) / 256;
+    return (int)(g > RCOT_SUMSQ_MAX_PARTS ? RCOT_SUMSQ_MAX_PARTS : g < 1 ? 1 : g);
+}
+
+int rcot_grad_sumsq(const float* g, long n, double* partials, void* stream) {
+    if (!g || !partials || n <= 0 || (reinterpret_cast<uintptr_t>(g) & 3) || (reinterpret_cast<uintptr_t>(partials) & 7)) return RCOT_EINVAL;
+    long head = (long)(((16 - (reinterpret_cast<uintptr_t>(g) & 15)) & 15) >> 2);   // elements before the first 16-byte boundary
+    if (head > n) head = n;
+    RCOT_LAUNCH(sumsq_kernel, dim3(rcot_grad_sumsq_parts(n)), dim3(256), 0, (hipStream_t)stream, g, n, (int)head, partials);
+    RCOT_LAUNCH_CHECK();
+    return RCOT_OK;
+}
+
+int rcot_grad_decide(const double* partials, int nparts, double* ctrl, int flags, double b1, double b2, void* stream) {
+    if (!partials || !ctrl || nparts <= 0 || nparts > RCOT_SUMSQ_MAX_PARTS || (flags & ~7) || (reinterpret_cast<uintptr_t>(partials) & 7) ||
+        (reinterpret_cast<uintptr_t>(ctrl) & 7))
+        return RCOT_EINVAL;
+    RCOT_LAUNCH(decide_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, nparts, ctrl, flags, b1, b2);
+    RCOT_LAUNCH_CHECK();
+    return RCOT_OK;
+}
+
+int rcot_rmsprop_step_guarded(float* p, const float* g, float* sq, long n, double alpha, double eps, const double* ctrl, void* stream) {
+    if (!p || !g || !sq || !ctrl || n <= 0 || (n & 3) || !al16(p) || !al16(g) || !al16(sq) || (reinterpret_cast<uintptr_t>(ctrl) & 7))
+        return RCOT_EINVAL;
+    const long n4 = n >> 2;
+    RCOT_LAUNCH(rmsprop_guarded_kernel, dim3((int)step_grid(n4)), dim3(256), 0, (hipStream_t)stream, (float4*)p, (const float4*)g,
+                (float4*)sq, n4, (float)alpha, (float)(1.0 - alpha), (float)eps, ctrl);
+    RCOT_LAUNCH_CHECK();
+    return RCOT_OK;
+}
+
+int rcot_adam_step_guarded(float* p, const float* g, float* m, float* v, long n, double b1, double b2, double eps, const double* ctrl,
+                           int counter, void* stream) {
+    if (!p || !g || !m || !v || !ctrl || n <= 0 || (n & 3) || counter < 0 || counter > 1 || !al16(p) || !al16(g) || !al16(m) || !al16(v) ||
+        (reinterpret_cast<uintptr_t>(ctrl) & 7))
+        return RCOT_EINVAL;
+    const long n4 = n >> 2;
+    RCOT_LAUNCH(adam_guarded_kernel, dim3((int)step_grid(n4)), dim3(256), 0, (hipStream_t)stream, (float4*)p, (const float4*)g, (float4*)m,
+                (float4*)v, n4, (float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), (float)eps, ctrl, counter);
     RCOT_LAUNCH_CHECK();
     return RCOT_OK;
 }

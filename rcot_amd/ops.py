@@ -1620,3 +1620,28 @@ class HipBackend:
     def ema_step(self, ema, p, n, decay):
         """ema[0:n) += (1 - decay) (p[0:n) - ema[0:n)) in one launch (rcot_amd/ema.py); any n >= 1, any fp32 alignment"""
         _lib.check(self.L.rcot_ema_step(ema.data_ptr(), p.data_ptr(), n, decay, self._st()), "rcot_ema_step")
+
+    # ---- gradient-norm clipping / non-finite skip decided on the device (control block: include/rcot_hip.h; trainer.FlatOptimizer)
+    def grad_sumsq(self, g, n, partials):
+        """partials[0:count) <- per-workgroup fp64 sums of g[0:n)^2; returns count (what grad_decide sums).  ``partials``: float64,
+        at least lib.SUMSQ_MAX_PARTS elements."""
+        if partials.dtype != torch.float64 or partials.numel() < _lib.SUMSQ_MAX_PARTS:
+            raise _lib.RcotKernelError("grad_sumsq: invalid argument: the workspace must hold 4096 float64 values")
+        _lib.check(self.L.rcot_grad_sumsq(g.data_ptr(), n, partials.data_ptr(), self._st()), "rcot_grad_sumsq")
+        return self.L.rcot_grad_sumsq_parts(n)
+
+    def grad_decide(self, partials, nparts, ctrl, adam_mask=0, b1=0.9, b2=0.999, inherit=False):
+        """norm, clip scale, skip flag and counters of one step into the control block ``ctrl`` (float64 [lib.CB_WORDS]), on the device.
+        ``inherit``: skip also when the block's previous decision skipped (a later step on the same batch; lib.DECIDE_INHERIT)"""
+        if ctrl.dtype != torch.float64 or ctrl.numel() < _lib.CB_WORDS:
+            raise _lib.RcotKernelError("grad_decide: invalid argument: the control block is float64 [16]")
+        _lib.check(self.L.rcot_grad_decide(partials.data_ptr(), nparts, ctrl.data_ptr(), adam_mask | (_lib.DECIDE_INHERIT if inherit else 0), b1, b2,
+                                           self._st()), "rcot_grad_decide")
+
+    def rmsprop_step_guarded(self, p, g, sq, n, ctrl, alpha=0.99, eps=1e-8):
+        _lib.check(self.L.rcot_rmsprop_step_guarded(p.data_ptr(), g.data_ptr(), sq.data_ptr(), n, alpha, eps, ctrl.data_ptr(), self._st()),
+                   "rcot_rmsprop_step_guarded")
+
+    def adam_step_guarded(self, p, g, m, v, n, ctrl, counter, b1=0.9, b2=0.999, eps=1e-8):
+        _lib.check(self.L.rcot_adam_step_guarded(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, b1, b2, eps, ctrl.data_ptr(),
+                                                 counter, self._st()), "rcot_adam_step_guarded")

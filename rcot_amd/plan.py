@@ -28,7 +28,7 @@ import torch
 
 from . import lib as _lib
 
-_HOST_ONLY = {"rcot_abi_version", "rcot_debug_nt_coop", "rcot_ln_bwd_rows", "rcot_last_kernel", "rcot_kmajor_desc_size", "rcot_profile_begin", "rcot_profile_end", "rcot_fft_plan", "rcot_attn_rows_ws_bytes"}          # no launch, no stream argument
+_HOST_ONLY = {"rcot_abi_version", "rcot_debug_nt_coop", "rcot_ln_bwd_rows", "rcot_last_kernel", "rcot_kmajor_desc_size", "rcot_profile_begin", "rcot_profile_end", "rcot_fft_plan", "rcot_attn_rows_ws_bytes", "rcot_grad_sumsq_parts"}          # no launch, no stream argument
 
 
 class _RecordingLib:
@@ -237,6 +237,8 @@ class PlannedMinimax:
         out = [st.T.store.flat, st.F.store.flat]
         for o in (st.To, st.Fo):
             out += list(o._state_tensors().values())
+            if getattr(o, "ctrl", None) is not None:    # a guarded optimizer's control block: the warm-up pass leaves no phantom counts
+                out.append(o.ctrl)
         if st.ema is not None:                   # the warm-up pass must not leave a phantom update in the weight average either
             out.append(st.ema.buf)
         return out

@@ -5,7 +5,8 @@ structure (critic step -> separate gradient-penalty step -> generator step, :262
 (:348-354) and checkpoint naming/keys (:362-371).  The compute is done by ``rcot_amd.net_restormer``
 (HIP kernels); this file only sequences it.  Additions are supersets: ``--seed``, ``--synthetic``,
 ``--iters``, data-parallel launch through torchrun (one process per GPU, RCCL), ``--ema`` / ``--val_weights`` (an exponential
-moving average of the transport map's weights: validated, saved next to the raw weights; rcot_amd/ema.py).
+moving average of the transport map's weights: validated, saved next to the raw weights; rcot_amd/ema.py), ``--clip_grad_norm`` /
+``--clip_grad_norm_F`` (gradient-norm clipping and a skip of steps with non-finite gradients, decided on the device: FlatOptimizer).
 """
 from __future__ import annotations
 
@@ -17,6 +18,7 @@ from typing import Optional, Sequence
 
 import torch
 
+from . import lib as _lib
 from . import parallel as par
 from .net_restormer import F_net, T_net
 
@@ -96,6 +98,12 @@ parser.add_argument("--ema", type=float, default=0.0,
 parser.add_argument("--val_weights", choices=["ema", "raw", "both"], default=None,
                     help="with --ema: the weights the per-epoch validation runs on (default ema); both writes psnr (the average) and "
                          "psnr_raw")
+parser.add_argument("--clip_grad_norm", type=float, default=0.0,
+                    help="guard the transport map's optimizer step: scale its gradients so that their L2 norm is at most M (the rule of "
+                         "torch.nn.utils.clip_grad_norm_; the Restormer recipe uses 0.01) and skip a step whose gradients are not finite, "
+                         "both decided on the device; inf = skip only.  0 = off, everything as before")
+parser.add_argument("--clip_grad_norm_F", type=float, default=0.0,
+                    help="the same for the potential, on both of its steps (critic and gradient penalty), each with its own norm")
 parser.add_argument("--synthetic", action="store_true", help="seeded synthetic patches (no dataset folders needed)")
 parser.add_argument("--iters", type=int, default=20, help="iterations per epoch with --synthetic")
 
@@ -139,6 +147,42 @@ def check_ema_flags(o, stock_mprnet: bool = False) -> None:
         raise SystemExit(f"--val_weights {o.val_weights} chooses between the raw weights and their average: it needs --ema D")
 
 
+def check_max_norm(m) -> float:
+    """the cap of a guarded optimizer: a number > 0, math.inf included (guard only).  Raises ValueError naming the value."""
+    m = float(m)
+    if not m > 0.0:                                                        # refuses NaN too
+        raise ValueError(f"max_norm {m}: the gradient-norm cap must be > 0 (inf = skip non-finite steps only)")
+    return m
+
+
+def check_clip_flags(o, stock_mprnet: bool = False) -> None:
+    """--clip_grad_norm / --clip_grad_norm_F M need M > 0 (inf allowed; 0, the default, is off) and optimizers over flat buffers (not the
+    stock-ops MPRNet loop).  Refused up front with SystemExit naming the flag and the value."""
+    for flag in ("clip_grad_norm", "clip_grad_norm_F"):
+        v = getattr(o, flag)
+        if v == 0.0:
+            continue
+        try:
+            check_max_norm(v)
+        except ValueError:
+            raise SystemExit(f"--{flag} {v}: the cap on the gradient norm must be > 0 (inf = only skip non-finite steps; 0 = off)")
+        if stock_mprnet:
+            raise SystemExit(f"--{flag} needs the fused optimizers over a flat parameter store: --backbone mprnet on stock PyTorch ops (no "
+                             "GPU visible, or RCOT_MPRNET_STOCK=1) has none")
+
+
+def guard_report(name: str, now: dict, before: Optional[dict]) -> str:
+    """the per-epoch line of a guarded optimizer from its counters (``now``) and those at the start of the epoch (``before``).  Raises
+    SystemExit when the epoch made decisions and every one of them was a skip: the run is not training any more."""
+    b = before or {"steps": 0, "clipped": 0, "skipped": 0}
+    steps, clipped, skipped = (now[k] - b[k] for k in ("steps", "clipped", "skipped"))
+    line = (f"clip {name}: max_norm {now['max_norm']:g}, steps {steps}, clipped {clipped}, skipped {skipped}, last norm {now['last_norm']:.6g}, "
+            f"largest norm {now['max_seen']:.6g} (run so far: {now['steps']} steps, {now['skipped']} skipped)")
+    if steps > 0 and skipped == steps:
+        raise SystemExit(f"{line}\n{name}: every optimizer step of this epoch was skipped (non-finite gradients): the run has stopped training")
+    return line
+
+
 def check_patch_size(P: int) -> int:
     """The training patch sizes the networks take: a multiple of 32 with 32 <= P <= 1024.  F_net halves the patch with five
     stride-2 convolutions (P/32 must be whole) and sizes its first fc layer as P*P/2 (Net_Restormer.py F_net: num_fea); the
@@ -173,7 +217,7 @@ def unfreeze(model):    # utils.py:28-31
 class FlatOptimizer:
     """RMSprop / Adam with torch defaults over a network's flat buffers (one fused launch)."""
 
-    def __init__(self, net, kind: str, lr: float):
+    def __init__(self, net, kind: str, lr: float, max_norm: Optional[float] = None):
         self.net, self.kind, self.lr = net, kind, lr
         st = net.store
         be = net.be
@@ -186,17 +230,45 @@ class FlatOptimizer:
             self.t_main, self.t_tail = 0, 0
         else:
             raise ValueError(kind)
+        #: None (the default): the plain launches, nothing allocated.  A value M > 0 (math.inf = guard only): every step is a guarded
+        #: step — the gradient norm of the stepped range is taken on the device, the gradients are scaled by min(1, M / (norm + 1e-6)) and
+        #: a step whose gradients are not finite is skipped — decided by kernels that read and write the control block ``ctrl``
+        #: (include/rcot_hip.h RCOT_CB_*: learning rate, counters, Adam's step counts), with no host read
+        self.max_norm = None if max_norm is None else check_max_norm(max_norm)
+        self.ctrl = self.partials = None
+        if self.max_norm is not None:
+            self.ctrl = torch.zeros(_lib.CB_WORDS, dtype=torch.float64, device=be.device)
+            self.partials = torch.zeros(_lib.SUMSQ_MAX_PARTS, dtype=torch.float64, device=be.device)
+            self.ctrl[_lib.CB_MAX_NORM] = self.max_norm
+            self._lr_written = None
+            self.sync_lr()
 
-    def step(self, n_live: Optional[int] = None):
+    def sync_lr(self):
+        """Guarded steps read their learning rate from the control block: bring it to ``param_groups[0]["lr"]`` by a stream-ordered
+        write when the two differ.  Called before every iteration, eager or replayed, and never recorded into a launch plan (a plan
+        records library launches only)."""
+        if self.ctrl is None:
+            return
+        lr = float(self.param_groups[0]["lr"])
+        if lr != self._lr_written:
+            self.ctrl[_lib.CB_LR:_lib.CB_LR + 1].fill_(lr)
+            self._lr_written = lr
+
+    def step(self, n_live: Optional[int] = None, same_batch: bool = False):
         """Update params[0:n_live) (default: every live parameter).  A shorter range reproduces
-        autograd's 'grad is None -> skipped' for the trailing tensors (fc2.bias in the GP step)."""
+        autograd's 'grad is None -> skipped' for the trailing tensors (fc2.bias in the GP step).
+        ``same_batch`` (guarded optimizers only; ignored otherwise): this step's gradients come from the batch of the previous step,
+        so it is skipped as well when that one was — the gradient-penalty step after a critic step whose target held a NaN: the
+        penalty's own gradients are finite there (products of weights and LeakyReLU masks) and mean nothing."""
         st, be = self.net.store, self.net.be
         lr = self.param_groups[0]["lr"]
         full = st.layout.n_live
         n = full if n_live is None else n_live
         n4 = (n + 3) // 4 * 4 if n < full else full
         n4 = min(n4, st.layout.n_total)
-        if self.kind == "RMSprop":
+        if self.ctrl is not None:
+            self._step_guarded(n, n4, full, same_batch)
+        elif self.kind == "RMSprop":
             be.rmsprop_step(st.flat, st.grad, self.sq, n4, lr)
         else:
             self.t_main += 1
@@ -208,6 +280,31 @@ class FlatOptimizer:
         if hasattr(self.net, "repack"):
             self.net.repack()            # private K-major weight copies follow the parameters
 
+    def _step_guarded(self, n, n4, full, same_batch=False):
+        """the same ranges as the plain step, behind one decision: the norm is that of grad[0:n4), the range stepped over (in the
+        gradient-penalty step it leaves out fc2.bias, whose gradient autograd leaves None); with several ranks it is taken from the
+        all-reduced buffer, so every rank decides alike"""
+        st, be = self.net.store, self.net.be
+        self.sync_lr()
+        parts = be.grad_sumsq(st.grad, n4, self.partials)
+        if self.kind == "RMSprop":
+            be.grad_decide(self.partials, parts, self.ctrl, inherit=same_batch)
+            be.rmsprop_step_guarded(st.flat, st.grad, self.sq, n4, self.ctrl)
+            return
+        o = self._tail_start()
+        tail = n >= full and o < full
+        be.grad_decide(self.partials, parts, self.ctrl, adam_mask=3 if tail else 1, inherit=same_batch)      # the counts advance on the device, unless skipped
+        be.adam_step_guarded(st.flat, st.grad, self.m, self.v, min(n4, o), self.ctrl, 0)
+        if tail:
+            be.adam_step_guarded(st.flat[o:], st.grad[o:], self.m[o:], self.v[o:], st.layout.n_total - o, self.ctrl, 1)
+
+    def guard_counters(self):
+        """{max_norm, steps, clipped, skipped, max_seen, last_norm, last_scale} read from the control block (one device read)"""
+        c = self.ctrl.cpu()
+        i = c.view(torch.int64)
+        return {"max_norm": self.max_norm, "steps": int(i[_lib.CB_STEPS]), "clipped": int(i[_lib.CB_CLIPPED]), "skipped": int(i[_lib.CB_SKIPPED]),
+                "max_seen": float(c[_lib.CB_MAX_SEEN]), "last_norm": float(c[_lib.CB_NORM]), "last_scale": float(c[_lib.CB_SCALE])}
+
     def _tail_start(self):
         """Offset of tensors that skip some steps (their Adam step count differs)."""
         lay = self.net.store.layout
@@ -218,10 +315,20 @@ class FlatOptimizer:
         return {k: getattr(self, k) for k in ("sq", "m", "v") if hasattr(self, k)}
 
     def state_dict(self):
-        """Optimizer state keyed by the reference's state_dict names (layout-independent), plus the step counters."""
+        """Optimizer state keyed by the reference's state_dict names (layout-independent), plus the step counters (read from the
+        control block when the optimizer is guarded) and, only then, "guard": {max_norm, steps, clipped, skipped, max_seen}."""
         st = self.net.store
-        out = {"kind": self.kind, "lr": self.param_groups[0]["lr"], "t_main": getattr(self, "t_main", 0),
-               "t_tail": getattr(self, "t_tail", 0), "state": {}}
+        t_main, t_tail = getattr(self, "t_main", 0), getattr(self, "t_tail", 0)
+        guard = None
+        if self.ctrl is not None:
+            g = self.guard_counters()
+            guard = {k: g[k] for k in ("max_norm", "steps", "clipped", "skipped", "max_seen")}
+            if self.kind == "Adam":
+                t = self.ctrl.cpu().view(torch.int64)
+                t_main, t_tail = int(t[_lib.CB_T]), int(t[_lib.CB_T + 1])
+        out = {"kind": self.kind, "lr": self.param_groups[0]["lr"], "t_main": t_main, "t_tail": t_tail, "state": {}}
+        if guard is not None:
+            out["guard"] = guard
         for key, flat in self._state_tensors().items():
             d = {}
             for name, shp in st.shapes:
@@ -244,10 +351,22 @@ class FlatOptimizer:
                 flat[o:o + t.numel()].copy_(t.reshape(-1).to(flat.dtype))
         if self.kind == "Adam":
             self.t_main, self.t_tail = int(sd.get("t_main", 0)), int(sd.get("t_tail", 0))
+        if self.ctrl is not None:
+            # the counters continue (this run's own max_norm stays); Adam's step counts go into the block: the decision that advances
+            # them next forms the bias corrections from them
+            c = self.ctrl.cpu()
+            i = c.view(torch.int64)
+            g = sd.get("guard") or {}
+            i[_lib.CB_STEPS], i[_lib.CB_CLIPPED], i[_lib.CB_SKIPPED] = int(g.get("steps", 0)), int(g.get("clipped", 0)), int(g.get("skipped", 0))
+            c[_lib.CB_MAX_SEEN] = float(g.get("max_seen", 0.0))
+            i[_lib.CB_T], i[_lib.CB_T + 1] = int(sd.get("t_main", 0)), int(sd.get("t_tail", 0))
+            self.ctrl.copy_(c)
 
     def broadcast_state(self):
         for flat in self._state_tensors().values():
             par.broadcast_flat(flat, 0)
+        if self.ctrl is not None:
+            par.broadcast_flat(self.ctrl, 0)
 
     def zero_state(self):
         for t in (getattr(self, "sq", None), getattr(self, "m", None), getattr(self, "v", None)):
@@ -255,9 +374,9 @@ class FlatOptimizer:
                 t.zero_()
 
 
-def make_optimizers(Tnet, Fnet, name: str, lr: float):
-    """trainer.py:121-126: lr/2 for the transport map, lr for the potential."""
-    return FlatOptimizer(Tnet, name, lr / 2), FlatOptimizer(Fnet, name, lr)
+def make_optimizers(Tnet, Fnet, name: str, lr: float, max_norm_T: Optional[float] = None, max_norm_F: Optional[float] = None):
+    """trainer.py:121-126: lr/2 for the transport map, lr for the potential.  ``max_norm_*``: guarded steps (FlatOptimizer)."""
+    return FlatOptimizer(Tnet, name, lr / 2, max_norm_T), FlatOptimizer(Fnet, name, lr, max_norm_F)
 
 
 # ------------------------------------------------------------------------------- one minimax iteration
@@ -293,6 +412,8 @@ class MinimaxStep:
 
     def run(self, degraded, target, de_id, alpha, paired: bool):
         """One minimax iteration: replay of the recorded launch plan when available, else the eager launch sequence."""
+        self.To.sync_lr()                      # guarded optimizers read their learning rate from a device word: written here, never recorded
+        self.Fo.sync_lr()
         if self.planned is not None and self.grad_probe is None and self.comm_log is None:
             return self.planned.iteration(degraded, target, de_id, alpha, paired)
         return self.iteration(degraded, target, de_id, alpha, paired)
@@ -338,7 +459,7 @@ class MinimaxStep:
         self._comm_mark("F_gp", self.redF)
         if self.grad_probe is not None:
             self.grad_probe("F_gp")
-        self.Fo.step(F.n_live_gp)                                    # :308 (fc2.bias has no gradient)
+        self.Fo.step(F.n_live_gp, same_batch=True)                   # :308 (fc2.bias has no gradient); a guarded step follows a skipped critic step
         # ---------------- generator ("T-sub"), trainer.py:311-346
         F.zero_grad()
         fo = F.forward(out, save=True)                               # :319 (F has taken its two steps)
@@ -704,6 +825,7 @@ def main(argv=None):
     # data folders, data parallelism, validation, launch plans; without one (or with RCOT_MPRNET_STOCK=1) the stock-ops loop
     hip_mprnet = opt.backbone == "mprnet" and torch.cuda.is_available() and os.environ.get("RCOT_MPRNET_STOCK", "0") != "1"
     check_ema_flags(opt, stock_mprnet=opt.backbone == "mprnet" and not hip_mprnet)
+    check_clip_flags(opt, stock_mprnet=opt.backbone == "mprnet" and not hip_mprnet)
     if opt.backbone == "mprnet" and not hip_mprnet:
         return main_mprnet()
     if "RANK" in os.environ and "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) > 1:
@@ -738,7 +860,7 @@ def main(argv=None):
     else:
         Tnet = _make_net("T_net", decoder=True, seed=seed)                 # trainer.py:92
     Fnet = _make_net("F_net", patch_size=opt.patch_size, seed=seed + 1)    # :93
-    T_opt, F_opt = make_optimizers(Tnet, Fnet, opt.optimizer, opt.lr)
+    T_opt, F_opt = make_optimizers(Tnet, Fnet, opt.optimizer, opt.lr, opt.clip_grad_norm or None, opt.clip_grad_norm_F or None)
     from .compat import load_checkpoint
     ck = None
     if opt.resume:
@@ -800,10 +922,18 @@ def main(argv=None):
     stepper = MinimaxStep(Tnet, Fnet, T_opt, F_opt, opt.sigma, opt.Sigma, ema=avg)
     stepper.sample_dir = "./checksample/" + str(opt.type) + "/" if rank == 0 else None
     TLOSS, PLOSS = [], []
+    guarded = [(name, o) for name, o in (("T_net", T_opt), ("F_net", F_opt)) if o.ctrl is not None]
+    seen = {name: o.guard_counters() for name, o in guarded}               # (a resumed run continues its counters)
     for epoch in range(opt.start_epoch, opt.nEpochs + 1):
         t0 = time.time()
         a, b, c = train(loader, T_opt, F_opt, Tnet, Fnet, epoch, stepper)
         torch.cuda.synchronize()
+        for name, o in guarded:                                            # one read per epoch; every rank holds the same counters
+            now = o.guard_counters()
+            line = guard_report(name, now, seen[name])
+            seen[name] = now
+            if rank == 0:
+                print(line)
         if rank == 0:
             dt = time.time() - t0
             print(f"epoch {epoch}: {len(loader) * opt.batchSize / dt:.1f} patches/s")
