@@ -25,7 +25,7 @@ extern "C" {
 
 /* Bumped on EVERY signature change; returned by rcot_abi_version() (csrc/api.hip) and compared by the loader
  * (rcot_amd/lib.py ABI_VERSION, tests/test_abi.py) so that a stale prebuilt .so is refused, not mis-called. */
-#define RCOT_ABI_VERSION 38
+#define RCOT_ABI_VERSION 39
 
 /* Arithmetic of the MFMA products of the three GEMM-shaped entry points that take `prec` (rcot_gemm_kmajor,
  * rcot_conv1x1_wgrad, rcot_bmm_nt); operands and results are fp32 in memory either way.
@@ -576,6 +576,27 @@ int rcot_image_egress(const float* restored, const float* degraded, const unsign
  *                       misaligned: RCOT_EWORKSPACE, nothing is launched and stats is untouched. */
 int rcot_image_quality(const unsigned char* a, const unsigned char* b, int h, int w, int window, int space, double* stats, float* ws,
                        size_t ws_bytes, void* stream);
+
+/* ---- PSNR-B's sums and the border shave (csrc/quality.hip; rcot_amd/quality.py, the tester's --psnrb / --shave) -----------------------
+ * PSNR-B (Yim & Bovik 2011, basicsr's calculate_psnrb) adds a blocking-effect factor to the mean squared error: how much stronger the
+ * steps of the RESTORED image a across the borders of the codec's 8 x 8 blocks are than its steps elsewhere.  Images and `space` as for
+ * rcot_image_quality.  (oy, ox), each 0 .. 7, is the position of the image's first pixel inside the block grid (0 for a whole image,
+ * n mod 8 after n pixels were shaved from every side).  For a plane p of a, the horizontal pair (y, x), (y, x + 1), 0 <= x <= w - 2, is a
+ * border pair when (x + ox) mod 8 == 7 and an inner pair otherwise; vertical pairs alike with oy.
+ *  rcot_image_blockiness : stats long long[planes][5] (8-byte aligned; planes = 3 for rgb, 1 for y), per plane
+ *                            [0] sum (a - b)^2;  [1] D_hb, [2] D_hi: sum (p[y][x] - p[y][x+1])^2 over the horizontal border resp. inner
+ *                            pairs;  [3] D_vb, [4] D_vi: the same for the vertical pairs.  All exact (64-bit integers); the pair counts
+ *                            and the figure itself follow on the host (quality.blockiness_counts, psnrb_from_sums).
+ *                          RCOT_EINVAL for null pointers, a misaligned stats, h or w < 1, an unknown space, oy or ox outside 0 .. 7 (and
+ *                          beyond the grid: h > 32 * 65535); nothing is launched.  Bitwise reproducible: per-workgroup partials in
+ *                          ws, then one fixed-order pass in a second launch, no atomics.  ws needs 40 * planes * ceil(h / 32) *
+ *                          ceil(w / 63) bytes, 8-byte aligned; smaller or misaligned: RCOT_EWORKSPACE, nothing is launched and stats is
+ *                          untouched.  a and b may start at any byte.
+ *  rcot_crop_u8          : src uint8 [h][w][3] -> dst uint8 [hc][wc][3] (dense) = src[y0 : y0 + hc][x0 : x0 + wc], one launch; src and dst
+ *                          at any byte, not overlapping.  RCOT_EINVAL for null pointers, sizes < 1 or a rectangle that leaves the image. */
+int rcot_image_blockiness(const unsigned char* a, const unsigned char* b, int h, int w, int space, int oy, int ox, long long* stats,
+                          float* ws, size_t ws_bytes, void* stream);
+int rcot_crop_u8(const unsigned char* src, int h, int w, int y0, int x0, int hc, int wc, unsigned char* dst, void* stream);
 
 /* ---- views of an image and their weighted blend (csrc/views.hip; rcot_amd/tiles.py, the tester's --tile / --ensemble) -----------------
  * Tiled inference and the x8 geometric self-ensemble are one operation: several network outputs, each a mapped window of the image,

@@ -1,5 +1,7 @@
 // Standard image-quality figures on the device (rcot_amd/quality.py; the testers' --ssim_window / --color):
-//   rcot_image_quality : two uint8 HWC images -> the sums under PSNR and under the windowed SSIM of the usual protocols
+//   rcot_image_quality    : two uint8 HWC images -> the sums under PSNR and under the windowed SSIM of the usual protocols
+//   rcot_image_blockiness : two uint8 HWC images -> the sums under PSNR-B (the tester's --psnrb), and rcot_crop_u8, the border shave
+//                           (--shave): both at the end of this file
 //
 // Definitions (a, b: uint8 [h][w][3], data range 255)
 //   space  0 rgb : the three channels are three planes.
@@ -276,6 +278,234 @@ int rcot_image_quality(const unsigned char* a, const unsigned char* b, int h, in
     const double positions = (double)planes * (h >= win ? h - win + 1 : 0) * (w >= win ? w - win + 1 : 0);
     RCOT_LAUNCH(quality_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)q.part_s, (const long long*)q.part_i, nb,
                 elements, positions, stats);
+    RCOT_LAUNCH_CHECK();
+    return RCOT_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// rcot_image_blockiness: the sums under PSNR-B (Yim & Bovik 2011; quality.py's psnrb_from_sums) — per plane the squared error between
+// a and b and the squared steps of a between horizontal and vertical neighbours, apart for the pairs that cross a border of the
+// 8 x 8 block grid whose origin the caller gives.  Memory-bound: one workgroup takes a BTH x BTW tile of the image with one more row
+// below and one more column to the right of a, stages those bytes once as aligned dwords (as quality_kernel does; never a byte outside
+// the 3 h w of an image), and then handles the planes of the space in turn: every plane value of a is formed once, by the thread
+// that owns the pixel, which takes its right neighbour from the next lane and its lower one through LDS.  Everything is an integer and
+// exact; per-workgroup 64-bit partials go to the workspace and one workgroup adds them in a fixed order.  All addresses are 64-bit.
+// rcot_crop_u8: a rectangle of an HWC image to a dense buffer, a dword of the destination per thread.
+namespace {
+
+constexpr int BTH = 32, BTW = 63;                       // pixels of one workgroup (tests/test_psnrb_gpu.py places images around them):
+                                                        // with the halo column a staged row is 64 pixels, one wave
+
+struct BlockinessArgs {
+    const uint8_t* a;             // [h][w][3], the image whose steps are measured
+    const uint8_t* b;
+    long long* part;              // [planes][5][nbp]
+    int h, w, space, oy, ox;
+};
+
+// Thread (wave, lane) has column `lane` of the staged tile and its rows wave, wave + 4, ...: the right neighbour is the next lane's
+// value, the lower one crosses LDS once.  A workgroup's sums stay below 2^31 (2016 pixels x 255^2 = 1.3e8), so they are exact in 32
+// bits; the partials and everything after them are 64-bit.
+__global__ __launch_bounds__(256) void blockiness_kernel(BlockinessArgs q) {
+    constexpr int R = BTH + 1, C = BTW + 1;
+    static_assert(C == 64 && BTH % 4 == 0, "a staged row is one wave, the rows go round the four waves");
+    constexpr int LW = ((3 + 3 * C + 3) / 4) | 1;       // LDS words of one staged row: phase <= 3 + C pixels (odd: rows on different banks)
+    constexpr int NROW = R * LW, NST = (NROW + 255) / 256;
+    __shared__ uint32_t s_raw[2][NROW];                 // [image][row][LW]: byte k of a row's segment at LDS byte (its address & 3) + k
+    __shared__ int s_pa[R][C];                          // the plane of a
+    __shared__ int s_red[4][5];
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const int h = q.h, w = q.w;
+    const int y0 = blockIdx.y * BTH, x0 = blockIdx.x * BTW;
+    // a: the tile and its halo; b: the tile alone
+    const int nr[2] = {min(R, h - y0), min(BTH, h - y0)};
+    const int nb3[2] = {3 * min(C, w - x0), 3 * min(BTW, w - x0)};
+    const long w3 = 3L * w, nbytes = (long)h * w3, off0 = ((long)y0 * w + x0) * 3;
+    const uintptr_t lo[2] = {reinterpret_cast<uintptr_t>(q.a), reinterpret_cast<uintptr_t>(q.b)};
+
+    // Staging: one aligned dword per thread and step, all loads in flight together.  A dword is loaded whole when it lies inside the
+    // image's bytes and byte by byte, in a pass that only the workgroups at the two ends of the image enter, where it does not.
+    {
+        // step s of this thread in image `img`: the address of its dword; false: nothing to stage
+        auto locate = [&](int s, int img, uintptr_t& p) {
+            const int i = t + 256 * s, r = i / LW, j = i - r * LW;
+            const uintptr_t row = lo[img] + off0 + r * w3;                      // the first byte of the row's segment
+            p = (row & ~(uintptr_t)3) + 4 * j;
+            return i < NROW && r < nr[img] && p < row + nb3[img];
+        };
+        auto inside = [&](uintptr_t p, int img) { return p >= lo[img] && p + 4 <= lo[img] + nbytes; };
+        uint32_t v[2][NST];
+#pragma unroll
+        for (int img = 0; img < 2; ++img)
+#pragma unroll
+            for (int s = 0; s < NST; ++s) {
+                uintptr_t p;
+                v[img][s] = 0;
+                if (locate(s, img, p) && inside(p, img)) v[img][s] = *reinterpret_cast<const uint32_t*>(p);
+            }
+#pragma unroll
+        for (int img = 0; img < 2; ++img)
+#pragma unroll
+            for (int s = 0; s < NST; ++s)
+                if (t + 256 * s < NROW) s_raw[img][t + 256 * s] = v[img][s];
+        // uniform: the first dword of the tile may start before the image, the last one of its last row may end behind it
+        if (off0 < 4 || off0 + (nr[0] - 1) * w3 + nb3[0] + 3 > nbytes) {
+#pragma unroll
+            for (int img = 0; img < 2; ++img)
+#pragma unroll
+                for (int s = 0; s < NST; ++s) {
+                    uintptr_t p;
+                    if (locate(s, img, p) && !inside(p, img)) {                 // the same thread rewrites its own word
+                        uint32_t u = 0;
+#pragma unroll
+                        for (int k = 0; k < 4; ++k)
+                            if (p + k >= lo[img] && p + k < lo[img] + nbytes) u |= (uint32_t)*reinterpret_cast<const uint8_t*>(p + k) << (8 * k);
+                        s_raw[img][t + 256 * s] = u;
+                    }
+                }
+        }
+    }
+    __syncthreads();
+
+    const int planes = q.space == 0 ? 3 : 1;
+    const long nbp = (long)gridDim.x * gridDim.y, blk = (long)blockIdx.y * gridDim.x + blockIdx.x;
+    const int x = x0 + lane;
+    const bool incol = x < w, owned = lane < BTW && incol, hpair = x + 1 < w, hborder = ((x + q.ox) & 7) == 7;
+    // byte phase of row r of the staged tile: (phase of the tile's first byte + r 3 w) mod 4
+    const int ph[2] = {(int)((lo[0] + off0) & 3), (int)((lo[1] + off0) & 3)}, w3m = (int)(w3 & 3);
+    auto pixel = [&](int img, int r) {
+        return reinterpret_cast<const uint8_t*>(s_raw[img] + r * LW) + ((ph[img] + r * w3m) & 3) + 3 * lane;
+    };
+    for (int plane = 0; plane < planes; ++plane) {
+        int va[BTH / 4 + 1];
+#pragma unroll
+        for (int k = 0; k <= BTH / 4; ++k) {
+            const int r = wave + 4 * k;                                         // k == BTH / 4: the halo row, wave 0 alone
+            va[k] = 0;
+            if (r < nr[0] && incol) va[k] = plane_value(pixel(0, r), plane, q.space);
+            if (r < R) s_pa[r][lane] = va[k];
+        }
+        __syncthreads();
+
+        int se = 0, shb = 0, shi = 0, svb = 0, svi = 0;
+#pragma unroll
+        for (int k = 0; k < BTH / 4; ++k) {
+            const int r = wave + 4 * k, y = y0 + r;
+            const int right = __shfl_down(va[k], 1, 64);                        // every lane takes part; lane 63 owns nothing
+            if (owned && y < h) {
+                const int d = va[k] - plane_value(pixel(1, r), plane, q.space);
+                se += d * d;
+                if (hpair) {
+                    const int e = va[k] - right, e2 = e * e;
+                    shb += hborder ? e2 : 0;
+                    shi += hborder ? 0 : e2;
+                }
+                if (y + 1 < h) {
+                    const int e = va[k] - s_pa[r + 1][lane], e2 = e * e;
+                    const bool vborder = ((y + q.oy) & 7) == 7;
+                    svb += vborder ? e2 : 0;
+                    svi += vborder ? 0 : e2;
+                }
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            se += __shfl_xor(se, o, 64);
+            shb += __shfl_xor(shb, o, 64);
+            shi += __shfl_xor(shi, o, 64);
+            svb += __shfl_xor(svb, o, 64);
+            svi += __shfl_xor(svi, o, 64);
+        }
+        if (lane == 0) {
+            s_red[wave][0] = se;
+            s_red[wave][1] = shb;
+            s_red[wave][2] = shi;
+            s_red[wave][3] = svb;
+            s_red[wave][4] = svi;
+        }
+        __syncthreads();                                // also: every read of s_pa is behind, the next plane may overwrite it
+        if (t < 5) q.part[(plane * 5 + t) * nbp + blk] = (long long)s_red[0][t] + s_red[1][t] + s_red[2][t] + s_red[3][t];
+        // (s_red is written again only behind the next plane's first barrier)
+    }
+}
+
+// stats[planes][5] from the partials, one workgroup: the integer sibling of final_sums (common.h).  Stream s = plane * 5 + k (nbp int64
+// values at part[s * nbp ..)) belongs to wave s: strided per-lane sums (the loads of eight steps in flight, the sums in order), then a
+// tree over the 64 lanes.  Up to 16 streams.
+__global__ __launch_bounds__(1024) void blockiness_final_kernel(const long long* __restrict__ part, long nbp, int nstreams,
+                                                                long long* __restrict__ stats) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (wave >= nstreams) return;
+    const long long* __restrict__ p = part + wave * nbp;
+    long long n = 0;
+#pragma unroll 8
+    for (long b = lane; b < nbp; b += 64) n += p[b];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+    if (lane == 0) stats[wave] = n;
+}
+
+// dword i of the destination's aligned cover: destination bytes 4 i - pad .. 4 i - pad + 3 (pad = dst & 3), whole when all four exist
+__global__ __launch_bounds__(256) void crop_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, long w3, long off0,
+                                                      long wc3, long n, int pad, long nq) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < nq; i += gridDim.x * 256L) {
+        const long d0 = 4 * i - pad, first = d0 < 0 ? 0 : d0;
+        long row = first / wc3, col = first - row * wc3;
+        uint32_t u = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const long d = d0 + k;
+            if (d < first || d >= n) continue;
+            u |= (uint32_t)src[off0 + row * w3 + col] << (8 * k);
+            if (++col == wc3) {
+                col = 0;
+                ++row;
+            }
+        }
+        if (d0 >= 0 && d0 + 4 <= n) {
+            *reinterpret_cast<uint32_t*>(dst + d0) = u;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (d0 + k >= 0 && d0 + k < n) dst[d0 + k] = (uint8_t)(u >> (8 * k));
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int rcot_image_blockiness(const unsigned char* a, const unsigned char* b, int h, int w, int space, int oy, int ox, long long* stats,
+                          float* ws, size_t ws_bytes, void* stream) {
+    if (!a || !b || !stats || !ws || h < 1 || w < 1 || space < 0 || space > 1 || oy < 0 || oy > 7 || ox < 0 || ox > 7) return RCOT_EINVAL;
+    if (reinterpret_cast<uintptr_t>(stats) & 7) return RCOT_EINVAL;
+    const int planes = space == 0 ? 3 : 1;
+    const dim3 grid(cdiv(w, BTW), cdiv(h, BTH));
+    if (grid.y > 65535u) return RCOT_EINVAL;
+    const long nbp = (long)grid.x * grid.y;
+    if ((size_t)nbp * planes * 40 > ws_bytes || (reinterpret_cast<uintptr_t>(ws) & 7)) return RCOT_EWORKSPACE;
+    BlockinessArgs q;
+    q.a = a;
+    q.b = b;
+    q.part = reinterpret_cast<long long*>(ws);
+    q.h = h; q.w = w; q.space = space; q.oy = oy; q.ox = ox;
+    RCOT_LAUNCH(blockiness_kernel, grid, dim3(256), 0, (hipStream_t)stream, q);
+    RCOT_LAUNCH_CHECK();
+    RCOT_LAUNCH(blockiness_final_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const long long*)q.part, nbp, planes * 5, stats);
+    RCOT_LAUNCH_CHECK();
+    return RCOT_OK;
+}
+
+int rcot_crop_u8(const unsigned char* src, int h, int w, int y0, int x0, int hc, int wc, unsigned char* dst, void* stream) {
+    if (!src || !dst || h < 1 || w < 1 || y0 < 0 || x0 < 0 || hc < 1 || wc < 1 || hc > h - y0 || wc > w - x0) return RCOT_EINVAL;
+    const long wc3 = 3L * wc, n = hc * wc3;
+    const int pad = (int)(reinterpret_cast<uintptr_t>(dst) & 3);
+    const long nq = (pad + n + 3) / 4;
+    RCOT_LAUNCH(crop_u8_kernel, dim3(grid_for(nq)), dim3(256), 0, (hipStream_t)stream, src, dst, 3L * w, ((long)y0 * w + x0) * 3, wc3, n, pad,
+                nq);
     RCOT_LAUNCH_CHECK();
     return RCOT_OK;
 }

@@ -1608,6 +1608,45 @@ class HipBackend:
                    "rcot_image_quality")
         return stats
 
+    BLOCKINESS_TILE = (32, 63)                     # BTH x BTW of csrc/quality.hip: pixels of one workgroup
+
+    @classmethod
+    def image_blockiness_ws_bytes(cls, h: int, w: int, space: str) -> int:
+        """workspace bytes rcot_image_blockiness needs (include/rcot_hip.h): 40 per workgroup and plane, one workgroup per tile"""
+        th, tw = cls.BLOCKINESS_TILE
+        return 40 * (3 if space == "rgb" else 1) * (-(-h // th)) * (-(-w // tw))
+
+    def image_blockiness(self, a_u8, b_u8, space: str, oy: int = 0, ox: int = 0, ws=None):
+        """a_u8 (the restored image), b_u8 uint8 [h, w, 3] on the device -> int64 [planes, 5]: per plane of ``space`` ("rgb" | "y") the
+        squared-error sum between a and b and D_hb, D_hi, D_vb, D_vi, the squared steps of a across the borders of the 8 x 8 block grid
+        with origin (oy, ox) and elsewhere — what ``quality.psnrb_from_sums`` turns into PSNR-B.  Two launches (per-workgroup partials
+        in ``ws``, default the backend's workspace, then a fixed-order sum): rcot_image_blockiness."""
+        self._u8_image(a_u8, "image_blockiness")
+        h, w, _ = a_u8.shape
+        self._u8_image(b_u8, "image_blockiness", h, w)
+        if space not in self.SPACES:
+            raise _lib.RcotKernelError(f"image_blockiness: invalid argument: color space {space!r}, expected one of {tuple(self.SPACES)}")
+        ws = self.ws if ws is None else ws
+        stats = torch.empty(3 if space == "rgb" else 1, 5, dtype=torch.int64, device=self.device)
+        _lib.check(self.L.rcot_image_blockiness(a_u8.data_ptr(), b_u8.data_ptr(), h, w, self.SPACES[space], int(oy), int(ox),
+                                                stats.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(), self._st()),
+                   "rcot_image_blockiness")
+        return stats
+
+    def crop_u8(self, img_u8, y0: int, x0: int, hc: int, wc: int, out=None):
+        """img_u8 uint8 [h, w, 3] on the device -> uint8 [hc, wc, 3] (dense) = img_u8[y0:y0 + hc, x0:x0 + wc] in one launch (rcot_crop_u8):
+        the border shave of the metrics"""
+        self._u8_image(img_u8, "crop_u8")
+        h, w, _ = img_u8.shape
+        y0, x0, hc, wc = int(y0), int(x0), int(hc), int(wc)
+        if y0 < 0 or x0 < 0 or hc < 1 or wc < 1 or y0 + hc > h or x0 + wc > w:
+            raise _lib.RcotKernelError(f"crop_u8: invalid argument: {hc} x {wc} at ({y0}, {x0}) leaves the {h} x {w} image")
+        if out is None:
+            out = torch.empty(hc, wc, 3, dtype=torch.uint8, device=self.device)
+        self._u8_image(out, "crop_u8", hc, wc)
+        _lib.check(self.L.rcot_crop_u8(img_u8.data_ptr(), h, w, y0, x0, hc, wc, out.data_ptr(), self._st()), "rcot_crop_u8")
+        return out
+
     # ------------------------------------------------------------------ optimizers
     def rmsprop_step(self, p, g, sq, n, lr, alpha=0.99, eps=1e-8, grad_scale=1.0):
         _lib.check(self.L.rcot_rmsprop_step(p.data_ptr(), g.data_ptr(), sq.data_ptr(), n, lr, alpha, eps, grad_scale,

@@ -30,6 +30,9 @@ and basicsr's [5:-5], so no border rule is involved.  The metric is the mean of 
 same count, so this is the mean of the per-channel means); when h < win or w < win the map is empty: sum 0, count 0, metric NaN.
 
 PSNR is ``10 log10(255^2 / mean((a - b)^2))`` over the planes of the chosen space, ``inf`` at zero error (in ``rgb``: ``tester.psnr_uint8``).
+
+PSNR-B (``psnrb_u8``; the device's sums: rcot_image_blockiness, ``HipBackend.image_blockiness``) and the border shave of SR tables
+(``shave_u8``; rcot_crop_u8) are defined at the end of this file.
 """
 from __future__ import annotations
 
@@ -144,3 +147,91 @@ def quality_metrics(stats) -> dict:
     err = s[0] / s[1] if s[1] else float("nan")
     return dict(psnr=float("inf") if err == 0.0 else 10.0 * math.log10(255.0 * 255.0 / err),
                 ssim=s[2] / s[3] if s[3] else float("nan"))
+
+
+# ------------------------------------------------------------------------------- PSNR-B and the border shave
+# PSNR-B (Yim & Bovik, "Quality assessment of deblocked images", IEEE TIP 2011; basicsr's ``calculate_psnrb``) adds a blocking-effect
+# factor (BEF) to the mean squared error: how much stronger the steps of the RESTORED image ``a`` across the borders of the codec's
+# 8 x 8 blocks are than its steps elsewhere.  The block grid has an origin (oy, ox), each 0 .. 7: the position of the image's first pixel
+# inside the grid — 0 for a whole image, ``n % 8`` after ``n`` pixels were shaved from every side, so that the borders stay where the
+# codec put them.  For one plane p of a: the horizontal pair (y, x), (y, x + 1), 0 <= x <= w - 2, is a border pair when
+# (x + ox) % 8 == 7 and an inner pair otherwise; D_hb, D_hi are the sums of (p[y, x] - p[y, x + 1])^2 over the two classes and N_hb, N_hi
+# their pair counts; the vertical pairs give D_vb, D_vi, N_vb, N_vi with oy.  N_b = N_hb + N_vb, N_i = N_hi + N_vi; BEF = 0 when either is
+# 0 or min(h, w) < 2, else with D_B = (D_hb + D_vb) / N_b and D_C = (D_hi + D_vi) / N_i: BEF = (log2 8 / log2 min(h, w)) (D_B - D_C) when
+# D_B > D_C (decided in exact integers), else 0.  PSNR-B of the plane = 10 log10(255^2 / (mean (a - b)^2 + BEF)), inf at a zero
+# denominator; PSNR-B of the image = the mean over the planes (basicsr's per-channel mean; ``psnr_u8`` pools the planes instead).
+# With origin 0 and h, w multiples of 8 this is basicsr's calculate_psnrb and the MATLAB original (the ratio is the same on the 0 .. 1 and
+# the 0 .. 255 scale).  At other sizes basicsr's border counts are inconsistent with the pairs it sums (``arange(7, W - 1, 8)`` against
+# ``W // 8 - 1``); the rule here counts the pairs that exist.
+BLOCK = 8
+
+
+def shave_u8(img: np.ndarray, n: int) -> np.ndarray:
+    """[h, w, ...] -> [h - 2n, w - 2n, ...]: ``n`` pixels off every side (SR tables shave ``scale`` pixels before PSNR / SSIM)"""
+    if n < 0:
+        raise ValueError(f"shave {n}: expected an integer >= 0")
+    h, w = img.shape[:2]
+    if n and (h <= 2 * n or w <= 2 * n):
+        raise ValueError(f"shave {n}: nothing is left of {h} x {w} pixels")
+    return img[n:h - n, n:w - n]
+
+
+def _origin(oy: int, ox: int):
+    if not (0 <= oy < BLOCK and 0 <= ox < BLOCK):
+        raise ValueError(f"block-grid origin ({oy}, {ox}): expected 0 .. {BLOCK - 1} each")
+
+
+def blockiness_counts(h: int, w: int, oy: int = 0, ox: int = 0):
+    """(N_hb, N_hi, N_vb, N_vi): the pairs that exist in an h x w plane under the grid origin (oy, ox).  With origin 0 and h, w
+    multiples of 8 these are basicsr's (and the MATLAB original's) counts; at other sizes basicsr's border counts are inconsistent
+    with the pairs it sums (``arange(7, W - 1, 8)`` against ``W // 8 - 1``), and this rule counts the pairs that exist."""
+    _origin(oy, ox)
+    nxb = sum(1 for x in range(w - 1) if (x + ox) % BLOCK == BLOCK - 1)
+    nyb = sum(1 for y in range(h - 1) if (y + oy) % BLOCK == BLOCK - 1)
+    n_hb, n_vb = h * nxb, w * nyb
+    return n_hb, h * (w - 1) - n_hb, n_vb, w * (h - 1) - n_vb
+
+
+def blockiness_sums(a: np.ndarray, space: str, oy: int = 0, ox: int = 0) -> np.ndarray:
+    """int64 [planes, 4]: (D_hb, D_hi, D_vb, D_vi) of every plane of ``a`` — stats[:, 1:] of rcot_image_blockiness"""
+    _origin(oy, ox)
+    p = planes_u8(a, space)
+    _, h, w = p.shape
+    dh, dv = (p[:, :, :-1] - p[:, :, 1:]) ** 2, (p[:, :-1, :] - p[:, 1:, :]) ** 2
+    xb, yb = (np.arange(w - 1) + ox) % BLOCK == BLOCK - 1, (np.arange(h - 1) + oy) % BLOCK == BLOCK - 1
+    return np.stack([dh[:, :, xb].sum(axis=(1, 2)), dh[:, :, ~xb].sum(axis=(1, 2)),
+                     dv[:, yb, :].sum(axis=(1, 2)), dv[:, ~yb, :].sum(axis=(1, 2))], axis=1).astype(np.int64)
+
+
+def bef_from_sums(sums, h: int, w: int, oy: int = 0, ox: int = 0) -> float:
+    """the blocking-effect factor of one plane from its (D_hb, D_hi, D_vb, D_vi)"""
+    d_hb, d_hi, d_vb, d_vi = (int(v) for v in sums)
+    n_hb, n_hi, n_vb, n_vi = blockiness_counts(h, w, oy, ox)
+    n_b, n_i, d_b, d_c = n_hb + n_vb, n_hi + n_vi, d_hb + d_vb, d_hi + d_vi
+    if n_b == 0 or n_i == 0 or min(h, w) < 2 or d_b * n_i <= d_c * n_b:
+        return 0.0
+    return (math.log2(BLOCK) / math.log2(min(h, w))) * (d_b / n_b - d_c / n_i)
+
+
+def psnrb_from_sums(stats, h: int, w: int, oy: int = 0, ox: int = 0) -> float:
+    """``stats``: integers [planes][5], per plane (sum (a - b)^2, D_hb, D_hi, D_vb, D_vi) — what rcot_image_blockiness writes -> PSNR-B,
+    the mean over the planes.  The host path and the device path both end here, so they print the same floats."""
+    rows = stats.tolist() if hasattr(stats, "tolist") else stats
+    out = []
+    for row in rows:
+        den = int(row[0]) / (h * w) + bef_from_sums(row[1:5], h, w, oy, ox)
+        out.append(float("inf") if den == 0.0 else 10.0 * math.log10(255.0 * 255.0 / den))
+    return sum(out) / len(out)
+
+
+def blockiness_stats(a: np.ndarray, b: np.ndarray, space: str, oy: int = 0, ox: int = 0) -> np.ndarray:
+    """int64 [planes, 5]: the host's restatement of rcot_image_blockiness (``a`` is the restored image, ``b`` the target)"""
+    pa, pb = planes_u8(a, space), planes_u8(b, space)
+    if pa.shape != pb.shape:
+        raise ValueError("the two images differ in shape")
+    return np.concatenate([((pa - pb) ** 2).sum(axis=(1, 2))[:, None], blockiness_sums(a, space, oy, ox)], axis=1).astype(np.int64)
+
+
+def psnrb_u8(a: np.ndarray, b: np.ndarray, space: str, oy: int = 0, ox: int = 0) -> float:
+    """PSNR-B of the restored uint8 [h, w, 3] image ``a`` against the target ``b`` on the planes of ``space``"""
+    return psnrb_from_sums(blockiness_stats(a, b, space, oy, ox), a.shape[0], a.shape[1], oy, ox)

@@ -71,6 +71,15 @@ bytes ``python -m rcot_amd.chain`` writes for the same seed (after the degradati
 of 4, as for every task; the folder tool does not).  It is refused together with ``--sr_scale``, ``--jpeg_q``, ``--blur`` or
 ``--noise_sigma``.
 
+Superset: ``--psnrb`` also reports PSNR-B (Yim & Bovik 2011, basicsr's ``calculate_psnrb``; rcot_amd/quality.py), the figure the CAR rows
+of restoration tables carry next to PSNR and SSIM: one more line after the SSIM line, in the colour space of ``--color``, from the PNGs
+with ``--metrics folders`` and from rcot_image_blockiness on the 8-bit images already on the device with ``--metrics device``.
+``--shave N`` crops N pixels from every side of both 8-bit images before PSNR, SSIM and PSNR-B, as SR tables do with N = the scale (the
+PNGs stay full size; PSNR-B keeps the codec's block grid, origin N mod 8; an image with nothing left is skipped with a message).  With
+``--metrics device`` the crop is rcot_crop_u8 and needs ``--ssim_window uniform7|gauss11``: the egress kernel's own sums cannot be cropped.
+SR tables: ``--shave <scale> --color y --ssim_window gauss11``; CAR tables: ``--psnrb --color y``.  With neither flag everything runs as
+before.
+
 Superset: ``--weights ema`` restores with the averaged weights that ``rcot_amd.trainer --ema`` saves under "Tnet_ema" (either backbone); it
 exits with a message naming the key when the checkpoint has none.  The default ``raw`` reads "Tnet" as before.
 """
@@ -140,6 +149,12 @@ parser.add_argument("--chain", default=None, type=str,
 parser.add_argument("--weights", choices=["raw", "ema"], default="raw",
                     help="superset: ema = the averaged weights of a checkpoint written with rcot_amd.trainer --ema (its \"Tnet_ema\" key); "
                          "raw = \"Tnet\", everything as before")
+parser.add_argument("--psnrb", action="store_true",
+                    help="superset: also report PSNR-B (PSNR with the blocking-effect factor of Yim & Bovik 2011; the CAR rows of "
+                         "restoration tables) in the colour space of --color")
+parser.add_argument("--shave", type=int, default=0,
+                    help="superset: crop this many pixels from every side of both 8-bit images before PSNR, SSIM and PSNR-B (SR tables: "
+                         "the scale); the written PNGs stay full size; 0 = off, everything as before")
 parser.add_argument("--savedeg", default=None, type=str, help="superset: also write the 8-bit network input (with --sr_scale: the bicubic "
                                                              "baseline) as PNGs under this folder")
 
@@ -179,9 +194,20 @@ def _standard(opt) -> bool:
     return opt.ssim_window != "box2" or opt.color != "rgb"
 
 
-def evaluate_folders(path1: str, path2: str, ssim_window: str = "box2", color: str = "rgb"):
+def _nothing_left(h: int, w: int, shave: int) -> bool:
+    """``--shave``: an h x w image that the crop would empty is skipped, with this one line"""
+    if h > 2 * shave and w > 2 * shave:
+        return False
+    print(f"  skipped: {h} x {w} leaves nothing after --shave {shave}")
+    return True
+
+
+def evaluate_folders(path1: str, path2: str, ssim_window: str = "box2", color: str = "rgb", psnrb: bool = False, shave: int = 0):
     """evaluate.calculate_evaluation_floder (:65-106): mean / best / worst PSNR and SSIM over the sorted file pairs; with another
-    ``ssim_window`` / ``color`` the protocols of rcot_amd/quality.py"""
+    ``ssim_window`` / ``color`` the protocols of rcot_amd/quality.py.  ``path1`` holds the targets, ``path2`` the restored images.
+    ``shave``: that many pixels come off every side of both images first (a pair with nothing left is skipped with a message and does
+    not count).  ``psnrb``: three more values follow the six, mean / best / worst PSNR-B of the restored images on the planes of
+    ``color``, with the block-grid origin ``shave % 8``."""
     from PIL import Image
     if (ssim_window, color) == ("box2", "rgb"):
         psnr, ssim = psnr_uint8, ssim_image
@@ -189,16 +215,27 @@ def evaluate_folders(path1: str, path2: str, ssim_window: str = "box2", color: s
         from . import quality as Q
         psnr, ssim = (lambda x, y: Q.psnr_u8(x, y, color)), (lambda x, y: Q.ssim_windowed(x, y, ssim_window, color))
     a, b = sorted(os.listdir(path1)), sorted(os.listdir(path2))
-    ps, ss = [], []
+    ps, ss, pb, skipped = [], [], [], 0
     for n1, n2 in zip(a, b):
         i1 = np.array(Image.open(os.path.join(path1, n1)).convert("RGB"))
         i2 = np.array(Image.open(os.path.join(path2, n2)).convert("RGB"))
+        if shave:
+            if _nothing_left(i1.shape[0], i1.shape[1], shave) or _nothing_left(i2.shape[0], i2.shape[1], shave):
+                skipped += 1
+                continue
+            from .quality import shave_u8
+            i1, i2 = shave_u8(i1, shave), shave_u8(i2, shave)
         ps.append(psnr(i1, i2))
         ss.append(ssim(i1, i2))
+        if psnrb:
+            from .quality import psnrb_u8
+            pb.append(psnrb_u8(i2, i1, color, shave % 8, shave % 8))
     if not ps:
         nan = float("nan")
-        return nan, nan, nan, nan, nan, nan
-    return sum(ps) / len(b), sum(ss) / len(b), max(ps), max(ss), min(ps), min(ss)
+        return (nan,) * (9 if psnrb else 6)
+    n = len(b) - skipped
+    six = sum(ps) / n, sum(ss) / n, max(ps), max(ss), min(ps), min(ss)
+    return six + (sum(pb) / n, max(pb), min(pb)) if psnrb else six
 
 
 # ------------------------------------------------------------------------------- the network of a checkpoint
@@ -252,14 +289,25 @@ def restore(net, x: torch.Tensor, tile: int = 0, overlap: int = 32, mult: int = 
     return acc / cnt
 
 
-def _report(psnr, ssim, pmax, smax, pmin, smin, done, ssim_window="box2", color="rgb"):
+def _report(psnr, ssim, pmax, smax, pmin, smin, done, ssim_window="box2", color="rgb", psnrb=None, shave=0):
+    """``psnrb``: None, or (mean, best, worst) of ``--psnrb``"""
     if (ssim_window, color) != ("box2", "rgb"):
-        print(f"metrics: ssim {ssim_window}, color {color}")
+        print(f"metrics: ssim {ssim_window}, color {color}" + (", psnrb" if psnrb is not None else "") + (f", shave {shave}" if shave else ""))
     print("FID value: not computed (needs a pretrained Inception network; tester.py:115-118)")
     print("PSNR: Averyge {:.5f},   best {:.5f},   worst {:.5f}".format(psnr, pmax, pmin))
     print("SSIM: Averyge {:.5f},   best {:.5f},   worst {:.5f}".format(ssim, smax, smin))
-    return dict(images=done, psnr=psnr, ssim=ssim, psnr_best=pmax, psnr_worst=pmin, ssim_best=smax, ssim_worst=smin,
-                ssim_window=ssim_window, color=color)
+    r = dict(images=done, psnr=psnr, ssim=ssim, psnr_best=pmax, psnr_worst=pmin, ssim_best=smax, ssim_worst=smin,
+             ssim_window=ssim_window, color=color)
+    if psnrb is not None:
+        print("PSNR-B: Averyge {:.5f},   best {:.5f},   worst {:.5f}".format(*psnrb))
+        r.update(psnrb=psnrb[0], psnrb_best=psnrb[1], psnrb_worst=psnrb[2])
+    return r
+
+
+def _report_folders(opt, done):
+    """the report of ``--metrics folders``: the PNGs read back"""
+    v = evaluate_folders(opt.savetar, opt.save, opt.ssim_window, opt.color, opt.psnrb, opt.shave)
+    return _report(*v[:6], done, opt.ssim_window, opt.color, v[6:] if opt.psnrb else None, opt.shave)
 
 
 def _target_task(opt):
@@ -309,7 +357,8 @@ def _main_any_size(opt, net):
     deg_list = tar_list if task is not None else sorted(glob.glob(opt.degset + "*"))
     rng = np.random.default_rng(opt.seed)
     noisy = opt.noise_sigma is not None
-    sizes, stats = [], []
+    N, og = opt.shave, opt.shave % 8                                  # the shave and the block-grid origin it leaves
+    sizes, stats, bstats = [], [], []
     for index, (deg_name, tar_name) in enumerate(zip(deg_list, tar_list)):
         name = os.path.basename(tar_name)
         print("Processing ", deg_name)
@@ -343,6 +392,8 @@ def _main_any_size(opt, net):
         except ValueError as e:
             print(f"  skipped: {e}")
             continue
+        if N and _nothing_left(h, w, N):
+            continue
         tar_d = torch.from_numpy(np.ascontiguousarray(tar)).to(be.device)
         if opt.savedeg:
             Image.fromarray(np.ascontiguousarray(deg)).save(os.path.join(opt.savedeg, name))
@@ -354,19 +405,32 @@ def _main_any_size(opt, net):
         r = restore_any_size(net, x, mult, opt.pad, opt.tile, opt.overlap, opt.tile_window, opt.tile_batch, opt.ensemble)
         out_u8, res_u8, st = be.image_egress(r.out, h, w, degraded=r.x, target=tar_d, res_scale=3.0 if noisy else 2.0, want_out=True,
                                              want_res=True, want_stats=device_metrics and not standard)
+        tar_m, out_m = tar_d, out_u8                                  # the pair the metrics see: shaved on the device
+        if device_metrics and N:
+            tar_m, out_m = be.crop_u8(tar_d, N, N, h - 2 * N, w - 2 * N), be.crop_u8(out_u8, N, N, h - 2 * N, w - 2 * N)
         if device_metrics and standard:
-            st = be.image_quality(tar_d, out_u8, opt.ssim_window, opt.color)
+            st = be.image_quality(tar_m, out_m, opt.ssim_window, opt.color)
+        if device_metrics and opt.psnrb:
+            bstats.append(be.image_blockiness(out_m, tar_m, opt.color, og, og))
         Image.fromarray(res_u8.cpu().numpy()).save(os.path.join(opt.saveres, name))
         Image.fromarray(out_u8.cpu().numpy()).save(os.path.join(opt.save, name))
         Image.fromarray(np.ascontiguousarray(tar)).save(os.path.join(opt.savetar, name))
         sizes.append((h, w))
         stats.append(st)
     if not device_metrics:
-        return _report(*evaluate_folders(opt.savetar, opt.save, *proto), len(sizes), *proto)
+        return _report_folders(opt, len(sizes))
     if not sizes:
         nan = float("nan")
-        return _report(nan, nan, nan, nan, nan, nan, 0, *proto)
-    host = torch.stack(stats).cpu().tolist()                          # four numbers per image, read once
+        return _report(nan, nan, nan, nan, nan, nan, 0, *proto, (nan, nan, nan) if opt.psnrb else None, N)
+    pb = None
+    if opt.psnrb:                                                     # the five integers per plane ride behind the four numbers, as bits
+        from .quality import psnrb_from_sums
+        both = torch.stack([torch.cat([s, b.view(torch.float64).flatten()]) for s, b in zip(stats, bstats)]).cpu().numpy()
+        host, ints = both[:, :4].tolist(), np.ascontiguousarray(both[:, 4:]).view(np.int64).reshape(len(sizes), -1, 5)
+        v = [psnrb_from_sums(i, h - 2 * N, w - 2 * N, og, og) for i, (h, w) in zip(ints, sizes)]
+        pb = (sum(v) / len(v), max(v), min(v))
+    else:
+        host = torch.stack(stats).cpu().tolist()                      # four numbers per image, read once
     if standard:
         from .quality import quality_metrics
         m = [quality_metrics(s) for s in host]
@@ -374,7 +438,7 @@ def _main_any_size(opt, net):
     else:
         m = [image_metrics(s, h, w) for s, (h, w) in zip(host, sizes)]
         ps, ss = [v["psnr_u8"] for v in m], [v["ssim"] for v in m]
-    return _report(sum(ps) / len(ps), sum(ss) / len(ss), max(ps), max(ss), min(ps), min(ss), len(sizes), *proto)
+    return _report(sum(ps) / len(ps), sum(ss) / len(ss), max(ps), max(ss), min(ps), min(ss), len(sizes), *proto, pb, N)
 
 
 def main(argv=None):
@@ -384,6 +448,11 @@ def main(argv=None):
     if opt.ssim_window == "box2" and opt.color == "y" and opt.metrics == "device":
         raise SystemExit("--ssim_window box2 with --color y (the reference's 2 x 2 map on the luma plane) is computed on the host only: "
                          "use --metrics folders, or --ssim_window uniform7 | gauss11")
+    if opt.shave < 0:
+        raise SystemExit(f"--shave {opt.shave}: the number of pixels cropped from every side must be an integer >= 0 (0 = off)")
+    if opt.shave > 0 and opt.metrics == "device" and opt.ssim_window == "box2":
+        raise SystemExit("--shave with --metrics device crops the 8-bit images for rcot_image_quality; --ssim_window box2 comes from the "
+                         "egress kernel's own sums, which cannot be cropped: use --ssim_window uniform7 | gauss11, or --metrics folders")
     if opt.jpeg_q < 0 or opt.jpeg_q > 100:
         raise SystemExit(f"--jpeg_q {opt.jpeg_q}: the quality must be in 1 .. 100 (0 = off)")
     if opt.jpeg_q > 0 and (opt.sr_scale > 0 or opt.noise_sigma is not None):
@@ -437,6 +506,8 @@ def main(argv=None):
         if h % mult or w % mult or h == 0 or w == 0:
             print(f"  skipped: {h} x {w} is not a multiple of {mult} (the network's resampling levels)")
             continue
+        if opt.shave and _nothing_left(h, w, opt.shave):
+            continue
         x = torch.from_numpy(np.ascontiguousarray(deg.transpose(2, 0, 1))).float().div(255).unsqueeze(0)
         if noisy:
             x = x + torch.from_numpy(rng.normal(size=tar.transpose(2, 0, 1).shape) * opt.noise_sigma / 255.0).float()
@@ -450,7 +521,7 @@ def main(argv=None):
         save_image(out.cpu(), os.path.join(opt.save, name))
         save_image(gt, os.path.join(opt.savetar, name))
         done += 1
-    return _report(*evaluate_folders(opt.savetar, opt.save, opt.ssim_window, opt.color), done, opt.ssim_window, opt.color)
+    return _report_folders(opt, done)
 
 
 if __name__ == "__main__":
