@@ -211,7 +211,7 @@ int rcot_linear_dgrad(const float* dY, const float* W, float* dX, int B, int in,
 int rcot_linear_wgrad(const float* dY, const float* X, float* dW, int B, int in, int out, float beta, void* stream);
 
 /* ---- dense convolutions (implicit GEMM, fp32 MFMA) --------------------------------------------------------
- * Y = act(conv2d(X, Wt, stride, pad) + bias) [+ R]; act = LeakyReLU(lrelu) (1 = identity).
+ * Y = act(conv2d(X, Wt, stride, pad) + bias [+ R]); act = LeakyReLU(lrelu) (1 = identity; the residual goes in before it).
  * cmap 1/2 folds nn.PixelUnshuffle(2)/nn.PixelShuffle(2) into the store (Net_Restormer.py:90-91, 107-108).
  * replaces nn.Conv2d at Net_Restormer.py:117 (patch embed), :90,:107 (Down/Upsample), :326 (+inp_img, :375),
  * and F_net.features :443-487 (k5s1p2, k4s2p1, k3s1p1 + LeakyReLU 0.2). */

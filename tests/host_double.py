@@ -219,10 +219,10 @@ class TorchDouble:
     # ---- conv2d
     def conv2d_fwd(self, X, Wt, bias, Y, stride, pad, lrelu=1.0, cmap=0, R=None, mask=None, mslope=1.0):
         r = F.conv2d(X, Wt, bias, stride=stride, padding=pad)
+        if R is not None:                     # the residual goes in BEFORE the activation (epi_store; tests/test_mprnet_gpu.py pins it)
+            r = r + R
         if lrelu != 1.0:
             r = F.leaky_relu(r, lrelu)
-        if R is not None:
-            r = r + R
         if cmap == 1:
             r = F.pixel_unshuffle(r, 2)
         elif cmap == 2:
