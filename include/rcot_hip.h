@@ -25,7 +25,7 @@ extern "C" {
 
 /* Bumped on EVERY signature change; returned by rcot_abi_version() (csrc/api.hip) and compared by the loader
  * (rcot_amd/lib.py ABI_VERSION, tests/test_abi.py) so that a stale prebuilt .so is refused, not mis-called. */
-#define RCOT_ABI_VERSION 39
+#define RCOT_ABI_VERSION 40
 
 /* Arithmetic of the MFMA products of the three GEMM-shaped entry points that take `prec` (rcot_gemm_kmajor,
  * rcot_conv1x1_wgrad, rcot_bmm_nt); operands and results are fp32 in memory either way.
@@ -483,6 +483,54 @@ int rcot_grad_decide(const double* partials, int nparts, double* ctrl, int flags
 int rcot_rmsprop_step_guarded(float* p, const float* g, float* sq, long n, double alpha, double eps, const double* ctrl, void* stream);
 int rcot_adam_step_guarded(float* p, const float* g, float* m, float* v, long n, double b1, double b2, double eps, const double* ctrl,
                            int counter, void* stream);
+
+/* ---- AdamW: decoupled weight decay (torch.optim.AdamW) -----------------------------------------------------------------------
+ * rcot_adamw_step is rcot_adam_step, and rcot_adamw_step_guarded is rcot_adam_step_guarded, with one more argument, weight_decay.  Before
+ * Adam's update (the same per-element expression, the same skip flag, counters, bias corrections and alignment rules)
+ *     p[i] = fmaf(-(float)(lr * weight_decay), p[i], p[i])
+ * with lr * weight_decay formed in double: by the host for rcot_adamw_step, by the kernel from block.lr for the guarded form.  The increment
+ * form on purpose, as for the weight average above: the factor (float)(1 - lr * weight_decay), which is what a float mul_ applies, rounds
+ * 1 - 3e-8 (lr 3e-4, weight_decay 1e-4) to 1 - 2^-24 and so doubles the decay.  The gradient does not see the decay (it is not L2
+ * regularisation); a skipped guarded step applies none.  weight_decay == 0 runs Adam's launch unchanged: the bits of rcot_adam_step*.
+ * The same bytes as Adam's (four streams read, three written), one more FMA per element.
+ *  RCOT_EINVAL (nothing is launched): a negative or NaN weight_decay; whatever rcot_adam_step / rcot_adam_step_guarded refuse. */
+int rcot_adamw_step(float* p, const float* g, float* m, float* v, long n, double lr, double b1, double b2, double eps, int step,
+                    double grad_scale, double weight_decay, void* stream);
+int rcot_adamw_step_guarded(float* p, const float* g, float* m, float* v, long n, double b1, double b2, double eps, const double* ctrl,
+                            int counter, double weight_decay, void* stream);
+
+/* ---- per-iteration schedules held on the device (rcot_amd/schedule.py) -------------------------------------------------------
+ * A learning rate, or an EMA decay, that changes every iteration is not passed by value (a recorded launch keeps its by-value
+ * arguments): ONE small launch at the head of an iteration writes this iteration's values into device words, and the step and EMA
+ * kernels of the iteration read them.  The SCHEDULE BLOCK: RCOT_SB_WORDS 8-byte words, doubles (D) and 64-bit integers (I), 8-byte
+ * aligned, zero-filled by the caller before first use:
+ *     word  0  I  t            iterations advanced so far (advances only when a table is given)
+ *     word  1  D  lr           the table value handed out last
+ *     word  2  I  ema_updates  EMA updates counted so far
+ *     word  3  D  ema_decay    the target decay D of the EMA warm-up; 0 = no EMA word is maintained; written by the HOST only, once
+ *     word  4  D  ema_omd      the 1 - D_u that the next EMA update reads (rcot_ema_step_dev)
+ *     words 5 .. 7  reserved
+ * rcot_sched_advance: one workgroup, everything in double:
+ *     v = table[min(t, n_table - 1)];  *lr_dst0 = v * mult0;  *lr_dst1 = v * mult1;  block.lr = v;  t += 1
+ *     when ema_decay > 0:  ema_omd = 1 - min(D, (1 + u) / (10 + u)) with u = ema_updates;  ema_updates += 1
+ *   `table`: n_table doubles on the device, one rate per iteration; it is not written.  PAST ITS END THE LAST ENTRY HOLDS (the
+ *   reference's schedulers, util/schedulers.py, raise an IndexError or divide past their periods there).  table may be NULL: no rate
+ *   is written, t and lr stay, only the EMA words are maintained.  lr_dst0 / lr_dst1: usually the RCOT_CB_LR words of two control
+ *   blocks (mult 0.5 is exact: the transport map's lr / 2, trainer.py:121-126); a NULL destination is skipped.  Ordinary stores.
+ *  RCOT_EINVAL (nothing is launched): a null or not 8-byte-aligned sched; n_table <= 0 with a non-null table; a table or a
+ *  destination that is not 8-byte aligned.
+ * rcot_ema_step_dev: rcot_ema_step with omd = (float)*omd_word read from the device (the block's ema_omd word, or any device double):
+ *   the same expression (one kernel body serves both), the same vector / tail / misaligned forms, the same refusals, plus
+ *   RCOT_EINVAL for a null or not 8-byte-aligned omd_word. */
+#define RCOT_SB_WORDS 8
+#define RCOT_SB_T 0
+#define RCOT_SB_LR 1
+#define RCOT_SB_EMA_UPDATES 2
+#define RCOT_SB_EMA_DECAY 3
+#define RCOT_SB_EMA_OMD 4
+int rcot_sched_advance(double* sched, const double* table, int n_table, double* lr_dst0, double mult0, double* lr_dst1, double mult1,
+                       void* stream);
+int rcot_ema_step_dev(float* ema, const float* p, long n, const double* omd_word, void* stream);
 
 /* ---- the reference's OLDER transport map: MPRNet-style Net.T_net (Net.py:179-216) ----------------------------
  * Its 3x3 / 1x1 convolutions are rcot_conv2d_fwd / _dgrad / _wgrad (KH = KW = 3 or 1, no bias); these are the pieces between them

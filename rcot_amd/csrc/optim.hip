@@ -52,7 +52,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float4* __restrict__ p, const
 // vec: n4 float4 elements grid-stride, then the n - 4 n4 <= 3 tail elements by the first lanes of workgroup 0; else n scalars.
 __device__ __forceinline__ float ema_one(float e, float pv, float omd) { return __builtin_fmaf(omd, pv - e, e); }
 
-__global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ ema, const float* __restrict__ p, long n, float omd, int vec) {
+__device__ __forceinline__ void ema_body(float* __restrict__ ema, const float* __restrict__ p, long n, float omd, int vec) {
     const long t0 = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256;
     if (vec) {
         float4* __restrict__ e4 = (float4*)ema;
@@ -72,6 +72,17 @@ __global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ ema, const
     } else {
         for (long i = t0; i < n; i += stride) ema[i] = ema_one(ema[i], p[i], omd);
     }
+}
+
+__global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ ema, const float* __restrict__ p, long n, float omd, int vec) {
+    ema_body(ema, p, n, omd, vec);
+}
+
+// The same body with 1 - decay read from a device word (a uniform load of what an earlier rcot_sched_advance launch wrote): the decay of
+// an EMA warm-up changes every iteration, and a recorded launch carries no by-value argument that does.
+__global__ __launch_bounds__(256) void ema_dev_kernel(float* __restrict__ ema, const float* __restrict__ p, long n,
+                                                      const double* __restrict__ omd_word, int vec) {
+    ema_body(ema, p, n, (float)*omd_word, vec);
 }
 
 // ---- gradient-norm clipping and non-finite step skip, decided on the device (control block: include/rcot_hip.h, RCOT_CB_*) ----
@@ -194,12 +205,93 @@ __global__ __launch_bounds__(256) void adam_guarded_kernel(float4* __restrict__ 
         v[i] = vv;
     }
 }
+
+// AdamW (torch.optim.AdamW): decoupled weight decay p <- p - (lr wd) p before Adam's update, as one fused multiply-add in the increment
+// form — nlrwd = -(float)(lr wd), the product formed in double.  The factor form (float)(1 - lr wd) would round 1 - 3e-8 (lr 3e-4,
+// wd 1e-4) to 1 - 2^-24: twice the decay asked for.  Adam's bytes, plus one FMA per element; RCOT_ADAM is the expression of adam_kernel.
+#define RCOT_WD(c) pv.c = __builtin_fmaf(nlrwd, pv.c, pv.c);
+__global__ __launch_bounds__(256) void adamw_kernel(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ m,
+                                                    float4* __restrict__ v, long n4, float b1, float b2, float omb1, float omb2, float eps,
+                                                    float step_size, float rsqrt_bc2, float gscale, float nlrwd) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        float4 pv = p[i], gv = g[i], mv = m[i], vv = v[i];
+        RCOT_WD(x) RCOT_WD(y) RCOT_WD(z) RCOT_WD(w)
+        RCOT_ADAM(x) RCOT_ADAM(y) RCOT_ADAM(z) RCOT_ADAM(w)
+        p[i] = pv;
+        m[i] = mv;
+        v[i] = vv;
+    }
+}
+
+// adam_guarded_kernel with the decay: lr wd is formed here, in double, from the block's learning rate.
+__global__ __launch_bounds__(256) void adamw_guarded_kernel(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ m,
+                                                            float4* __restrict__ v, long n4, float b1, float b2, float omb1, float omb2,
+                                                            float eps, const double* __restrict__ ctrl, int counter, double wd) {
+    const long long* ci = reinterpret_cast<const long long*>(ctrl);
+    if (ci[RCOT_CB_SKIP] || ci[RCOT_CB_T + counter] <= 0) return;
+    const float step_size = (float)(ctrl[RCOT_CB_LR] / ctrl[RCOT_CB_BC1 + counter]);
+    const float rsqrt_bc2 = (float)(1.0 / sqrt(ctrl[RCOT_CB_BC2 + counter]));
+    const float gscale = (float)ctrl[RCOT_CB_SCALE];
+    const float nlrwd = -(float)(ctrl[RCOT_CB_LR] * wd);
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        float4 pv = p[i], gv = g[i], mv = m[i], vv = v[i];
+        RCOT_WD(x) RCOT_WD(y) RCOT_WD(z) RCOT_WD(w)
+        RCOT_ADAM(x) RCOT_ADAM(y) RCOT_ADAM(z) RCOT_ADAM(w)
+        p[i] = pv;
+        m[i] = mv;
+        v[i] = vv;
+    }
+}
+#undef RCOT_WD
 #undef RCOT_RMS
 #undef RCOT_ADAM
+
+// ---- per-iteration schedules held on the device (schedule block: include/rcot_hip.h, RCOT_SB_*) ----
+// ONE workgroup, one lane of it: the iteration's rate from the table into the block and into up to two destination words (the
+// RCOT_CB_LR words of the two optimizers), the counter, and the 1 - D_u of the EMA warm-up.  Every word written here is read by LATER
+// launches only.  Plain stores of doubles and 64-bit integers.
+__global__ __launch_bounds__(64) void sched_advance_kernel(double* __restrict__ sched, const double* __restrict__ table, int n_table,
+                                                           double* lr_dst0, double mult0, double* lr_dst1, double mult1) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    long long* si = reinterpret_cast<long long*>(sched);
+    if (table) {
+        const long long t = si[RCOT_SB_T];
+        long long idx = t < (long long)n_table - 1 ? t : (long long)n_table - 1;      // past the end the last entry holds
+        if (idx < 0) idx = 0;
+        const double v = table[idx];
+        if (lr_dst0) *lr_dst0 = v * mult0;
+        if (lr_dst1) *lr_dst1 = v * mult1;
+        sched[RCOT_SB_LR] = v;
+        si[RCOT_SB_T] = t + 1;
+    }
+    const double D = sched[RCOT_SB_EMA_DECAY];
+    if (D > 0.0) {
+        const long long u = si[RCOT_SB_EMA_UPDATES];
+        const double w = (1.0 + (double)u) / (10.0 + (double)u);
+        sched[RCOT_SB_EMA_OMD] = 1.0 - (D < w ? D : w);
+        si[RCOT_SB_EMA_UPDATES] = u + 1;
+    }
+}
 
 inline long step_grid(long n4) {
     long grid = (n4 + 255) / 256;
     return grid > 4096 ? 4096 : grid;
+}
+
+// what rcot_ema_step and rcot_ema_step_dev refuse alike (false), else the form (float4 body + tail, or scalar) and the grid
+inline bool ema_geometry(const float* ema, const float* p, long n, int* vec, long* grid) {
+    if (!ema || !p || n <= 0) return false;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(ema), b = reinterpret_cast<uintptr_t>(p);
+    if ((a & 3) || (b & 3)) return false;
+    const uintptr_t bytes = (uintptr_t)n * 4;
+    if (a < b + bytes && b < a + bytes) return false;                     // the ranges overlap
+    *vec = al16(ema) && al16(p);
+    const long items = *vec ? (n >> 2) : n;
+    long g = (items + 255) / 256;
+    if (g > 4096) g = 4096;
+    if (g < 1) g = 1;                                                     // n < 4 on the float4 path: the tail alone
+    *grid = g;
+    return true;
 }
 }  // namespace
 
@@ -238,17 +330,48 @@ int rcot_adam_step(float* p, const float* g, float* m, float* v, long n, double 
 // 1 - decay is formed in double, as 1 - alpha above.  Any n >= 1 and any 4-byte-aligned pointers: float4 accesses when both are
 // 16-byte aligned, a scalar grid-stride sweep otherwise.  !(0 <= decay < 1) also refuses NaN.
 int rcot_ema_step(float* ema, const float* p, long n, double decay, void* stream) {
-    if (!ema || !p || n <= 0 || !(decay >= 0.0 && decay < 1.0)) return RCOT_EINVAL;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(ema), b = reinterpret_cast<uintptr_t>(p);
-    if ((a & 3) || (b & 3)) return RCOT_EINVAL;
-    const uintptr_t bytes = (uintptr_t)n * 4;
-    if (a < b + bytes && b < a + bytes) return RCOT_EINVAL;              // the ranges overlap
-    const int vec = al16(ema) && al16(p);
-    const long items = vec ? (n >> 2) : n;
-    long grid = (items + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    if (grid < 1) grid = 1;                                             // n < 4 on the float4 path: the tail alone
+    if (!(decay >= 0.0 && decay < 1.0)) return RCOT_EINVAL;
+    int vec;
+    long grid;
+    if (!ema_geometry(ema, p, n, &vec, &grid)) return RCOT_EINVAL;
     RCOT_LAUNCH(ema_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, ema, p, n, (float)(1.0 - decay), vec);
+    RCOT_LAUNCH_CHECK();
+    return RCOT_OK;
+}
+
+// rcot_ema_step with omd = (float)*omd_word read on the device: the same refusals and the same three forms.
+int rcot_ema_step_dev(float* ema, const float* p, long n, const double* omd_word, void* stream) {
+    if (!omd_word || (reinterpret_cast<uintptr_t>(omd_word) & 7)) return RCOT_EINVAL;
+    int vec;
+    long grid;
+    if (!ema_geometry(ema, p, n, &vec, &grid)) return RCOT_EINVAL;
+    RCOT_LAUNCH(ema_dev_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, ema, p, n, omd_word, vec);
+    RCOT_LAUNCH_CHECK();
+    return RCOT_OK;
+}
+
+int rcot_adamw_step(float* p, const float* g, float* m, float* v, long n, double lr, double b1, double b2, double eps, int step,
+                    double grad_scale, double weight_decay, void* stream) {
+    if (!(weight_decay >= 0.0)) return RCOT_EINVAL;                        // refuses NaN too
+    if (weight_decay == 0.0) return rcot_adam_step(p, g, m, v, n, lr, b1, b2, eps, step, grad_scale, stream);
+    if (!p || !g || !m || !v || n <= 0 || (n & 3) || step <= 0 || !al16(p) || !al16(g) || !al16(m) || !al16(v))
+        return RCOT_EINVAL;
+    const long n4 = n >> 2;
+    const double bc1 = 1.0 - pow(b1, (double)step);
+    const double bc2 = 1.0 - pow(b2, (double)step);
+    RCOT_LAUNCH(adamw_kernel, dim3((int)step_grid(n4)), dim3(256), 0, (hipStream_t)stream, (float4*)p, (const float4*)g, (float4*)m,
+                (float4*)v, n4, (float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), (float)eps, (float)(lr / bc1),
+                (float)(1.0 / sqrt(bc2)), (float)grad_scale, -(float)(lr * weight_decay));
+    RCOT_LAUNCH_CHECK();
+    return RCOT_OK;
+}
+
+int rcot_sched_advance(double* sched, const double* table, int n_table, double* lr_dst0, double mult0, double* lr_dst1, double mult1,
+                       void* stream) {
+    if (!sched || (reinterpret_cast<uintptr_t>(sched) & 7) || (table && n_table <= 0) || (reinterpret_cast<uintptr_t>(table) & 7) ||
+        (reinterpret_cast<uintptr_t>(lr_dst0) & 7) || (reinterpret_cast<uintptr_t>(lr_dst1) & 7))
+        return RCOT_EINVAL;
+    RCOT_LAUNCH(sched_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, sched, table, n_table, lr_dst0, mult0, lr_dst1, mult1);
     RCOT_LAUNCH_CHECK();
     return RCOT_OK;
 }
@@ -296,6 +419,20 @@ int rcot_adam_step_guarded(float* p, const float* g, float* m, float* v, long n,
     const long n4 = n >> 2;
     RCOT_LAUNCH(adam_guarded_kernel, dim3((int)step_grid(n4)), dim3(256), 0, (hipStream_t)stream, (float4*)p, (const float4*)g, (float4*)m,
                 (float4*)v, n4, (float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), (float)eps, ctrl, counter);
+    RCOT_LAUNCH_CHECK();
+    return RCOT_OK;
+}
+
+int rcot_adamw_step_guarded(float* p, const float* g, float* m, float* v, long n, double b1, double b2, double eps, const double* ctrl,
+                            int counter, double weight_decay, void* stream) {
+    if (!(weight_decay >= 0.0)) return RCOT_EINVAL;
+    if (weight_decay == 0.0) return rcot_adam_step_guarded(p, g, m, v, n, b1, b2, eps, ctrl, counter, stream);
+    if (!p || !g || !m || !v || !ctrl || n <= 0 || (n & 3) || counter < 0 || counter > 1 || !al16(p) || !al16(g) || !al16(m) || !al16(v) ||
+        (reinterpret_cast<uintptr_t>(ctrl) & 7))
+        return RCOT_EINVAL;
+    const long n4 = n >> 2;
+    RCOT_LAUNCH(adamw_guarded_kernel, dim3((int)step_grid(n4)), dim3(256), 0, (hipStream_t)stream, (float4*)p, (const float4*)g, (float4*)m,
+                (float4*)v, n4, (float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), (float)eps, ctrl, counter, weight_decay);
     RCOT_LAUNCH_CHECK();
     return RCOT_OK;
 }

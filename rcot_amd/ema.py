@@ -54,10 +54,17 @@ class WeightAverage:
         self.buf = net.be.zeros(self.n)
         self.buf.copy_(st.flat)
         self.updates = 0
+        #: None: the constant decay, by value.  A one-element float64 device view (the ema_omd word of a rcot_amd.schedule.Schedule built
+        #: with ema_decay = this decay): every update reads its 1 - D_u from it (rcot_ema_step_dev) — the warm-up
+        #: D_u = min(D, (1 + u) / (10 + u)), which that schedule's advance launch forms once per iteration
+        self.omd_word = None
 
     def update(self):
         """one step of the average towards the current parameters: call it after the optimizer step"""
-        self.net.be.ema_step(self.buf, self.net.store.flat, self.n, self.decay)
+        if self.omd_word is not None:
+            self.net.be.ema_step_dev(self.buf, self.net.store.flat, self.n, self.omd_word)
+        else:
+            self.net.be.ema_step(self.buf, self.net.store.flat, self.n, self.decay)
         self.updates += 1
 
     @contextlib.contextmanager

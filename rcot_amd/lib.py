@@ -9,12 +9,14 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 39    # == RCOT_ABI_VERSION in include/rcot_hip.h (checked by tests/test_abi.py and at load time)
+ABI_VERSION = 40    # == RCOT_ABI_VERSION in include/rcot_hip.h (checked by tests/test_abi.py and at load time)
 PREC_FP32, PREC_BF16X3, PREC_BF16X6, PREC_BF16X1 = 0, 1, 2, 3     # RCOT_PREC_* of include/rcot_hip.h
 # the control block of a guarded optimizer (include/rcot_hip.h): word indices into a float64 tensor of CB_WORDS (the I words through .view(int64))
 SUMSQ_MAX_PARTS, CB_WORDS = 4096, 16
 DECIDE_ADAM0, DECIDE_ADAM1, DECIDE_INHERIT = 1, 2, 4               # flags of rcot_grad_decide
 CB_LR, CB_MAX_NORM, CB_NORM, CB_SCALE, CB_STEPS, CB_CLIPPED, CB_SKIPPED, CB_MAX_SEEN, CB_SKIP, CB_T, CB_BC1, CB_BC2 = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 11, 13
+# the schedule block of rcot_sched_advance (include/rcot_hip.h RCOT_SB_*): word indices into a float64 tensor of SB_WORDS
+SB_WORDS, SB_T, SB_LR, SB_EMA_UPDATES, SB_EMA_DECAY, SB_EMA_OMD = 8, 0, 1, 2, 3, 4
 LIB_PATH = os.environ.get("RCOT_LIB") or os.path.join(_HERE, "librcot_hip.so")   # RCOT_LIB: A/B builds while tuning
 
 
@@ -117,6 +119,11 @@ SIGNATURES = {
     "rcot_grad_decide": [_f, _i, _f, _i, _d, _d, _f],
     "rcot_rmsprop_step_guarded": [_f, _f, _f, _l, _d, _d, _f, _f],
     "rcot_adam_step_guarded": [_f, _f, _f, _f, _l, _d, _d, _d, _f, _i, _f],
+    # AdamW (decoupled weight decay), the schedule block's advance launch and the EMA step that reads 1 - decay from a device word
+    "rcot_adamw_step": [_f, _f, _f, _f, _l, _d, _d, _d, _d, _i, _d, _d, _f],
+    "rcot_adamw_step_guarded": [_f, _f, _f, _f, _l, _d, _d, _d, _f, _i, _d, _f],
+    "rcot_sched_advance": [_f, _f, _i, _f, _d, _f, _d, _f],
+    "rcot_ema_step_dev": [_f, _f, _l, _f, _f],
     # the MPRNet backbone's pointwise pieces (csrc/mprnet_ops.hip)
     "rcot_prelu_fwd": [_f, _f, _f, _l, _f],
     "rcot_prelu_bwd": [_f, _f, _f, _f, _f, _l, _f, _sz, _f],

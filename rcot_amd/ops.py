@@ -1684,3 +1684,32 @@ class HipBackend:
     def adam_step_guarded(self, p, g, m, v, n, ctrl, counter, b1=0.9, b2=0.999, eps=1e-8):
         _lib.check(self.L.rcot_adam_step_guarded(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, b1, b2, eps, ctrl.data_ptr(),
                                                  counter, self._st()), "rcot_adam_step_guarded")
+
+    # ---- AdamW, and the per-iteration schedule held on the device (schedule block: include/rcot_hip.h RCOT_SB_*; rcot_amd/schedule.py)
+    def adamw_step(self, p, g, m, v, n, lr, step, weight_decay, b1=0.9, b2=0.999, eps=1e-8, grad_scale=1.0):
+        """adam_step after the decoupled decay p <- p - (lr weight_decay) p (torch.optim.AdamW)"""
+        _lib.check(self.L.rcot_adamw_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, lr, b1, b2, eps, step, grad_scale,
+                                          weight_decay, self._st()), "rcot_adamw_step")
+
+    def adamw_step_guarded(self, p, g, m, v, n, ctrl, counter, weight_decay, b1=0.9, b2=0.999, eps=1e-8):
+        _lib.check(self.L.rcot_adamw_step_guarded(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, b1, b2, eps, ctrl.data_ptr(),
+                                                  counter, weight_decay, self._st()), "rcot_adamw_step_guarded")
+
+    def sched_advance(self, sched, table=None, lr_dst0=None, mult0=1.0, lr_dst1=None, mult1=1.0):
+        """one iteration of the schedule block ``sched`` (float64 [lib.SB_WORDS]): this iteration's entry of ``table`` (float64, on the
+        device; None = no rate) times mult0 / mult1 into the one-element float64 views lr_dst0 / lr_dst1 (None = skipped), the counter,
+        and the EMA warm-up's 1 - D_u when the block's ema_decay word is set.  One launch, no host read."""
+        if sched.dtype != torch.float64 or sched.numel() < _lib.SB_WORDS or (table is not None and table.dtype != torch.float64):
+            raise _lib.RcotKernelError("sched_advance: invalid argument: the schedule block is float64 [8], the table float64")
+        for d in (lr_dst0, lr_dst1):
+            if d is not None and (d.dtype != torch.float64 or d.numel() < 1):
+                raise _lib.RcotKernelError("sched_advance: invalid argument: a destination is a float64 word")
+        _lib.check(self.L.rcot_sched_advance(sched.data_ptr(), 0 if table is None else table.data_ptr(), 0 if table is None else table.numel(),
+                                             0 if lr_dst0 is None else lr_dst0.data_ptr(), mult0, 0 if lr_dst1 is None else lr_dst1.data_ptr(),
+                                             mult1, self._st()), "rcot_sched_advance")
+
+    def ema_step_dev(self, ema, p, n, omd_word):
+        """ema_step with 1 - decay read from the device double ``omd_word`` (a one-element float64 view)"""
+        if omd_word.dtype != torch.float64 or omd_word.numel() < 1:
+            raise _lib.RcotKernelError("ema_step_dev: invalid argument: omd_word is a float64 word")
+        _lib.check(self.L.rcot_ema_step_dev(ema.data_ptr(), p.data_ptr(), n, omd_word.data_ptr(), self._st()), "rcot_ema_step_dev")

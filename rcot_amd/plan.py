@@ -14,8 +14,10 @@ price of one ctypes call each (~2 us + the launch itself).  Host-driven steps in
 reducer's collectives, the few torch-side fills) are kept as Python callables at their position in the list.
 
 What makes this valid is what makes graph capture valid: static shapes, no host read of device values inside the region,
-scalars passed by value that do not change (the learning rate is part of the cache key; Adam's step count is not static, so
-Adam runs eagerly).  Recording executes the kernels (unlike a graph capture), so the recording pass IS a training iteration.
+scalars passed by value that do not change (the learning rate of the plain RMSprop launches is patched into the recorded calls
+when it changes; the plain Adam / AdamW launches take their step count by value, so they run eagerly; GUARDED steps of any kind read
+rate, counts and bias corrections from their control block and are recorded, and a per-iteration schedule is one more recorded launch
+that writes the rates into those blocks: rcot_amd/schedule.py).  Recording executes the kernels (unlike a graph capture), so the recording pass IS a training iteration.
 """
 from __future__ import annotations
 
@@ -228,8 +230,9 @@ class PlannedMinimax:
         self.warmup = warmup
         self._warmed = set()                     # (batch shape, arithmetic, spectral branch) that ran eagerly once
         self.enabled = step.T.store.flat.is_cuda and hasattr(torch.cuda, "MemPool")
-        # the Adam kernels take the step count BY VALUE (bias correction): not a static argument
-        if step.To.kind != "RMSprop" or step.Fo.kind != "RMSprop":
+        # the plain Adam / AdamW kernels take the step count BY VALUE (bias correction): not a static argument.  The guarded ones read it
+        # from their control block, where the decision launch advances it: nothing by-value changes between their iterations
+        if any(o.kind != "RMSprop" and getattr(o, "ctrl", None) is None for o in (step.To, step.Fo)):
             self.enabled = False
 
     def _state_tensors(self):
@@ -241,6 +244,8 @@ class PlannedMinimax:
                 out.append(o.ctrl)
         if st.ema is not None:                   # the warm-up pass must not leave a phantom update in the weight average either
             out.append(st.ema.buf)
+        if getattr(st, "schedule", None) is not None:    # nor a phantom advance in the schedule block
+            out.append(st.schedule.block)
         return out
 
     def _key(self, degraded, paired):
@@ -302,12 +307,16 @@ class PlannedMinimax:
             # iteration: parameters and optimizer state are put back.
             saved = [t.clone() for t in self._state_tensors()]
             ema_updates = st.ema.updates if st.ema is not None else 0
+            sched = getattr(st, "schedule", None)
+            sched_mirror = sched.mirror() if sched is not None else None
             for _ in range(self.warmup):
                 st.iteration(degraded, target, de_id, alpha, paired)
             for t, s_ in zip(self._state_tensors(), saved):
                 t.copy_(s_)
             if st.ema is not None:
                 st.ema.updates = ema_updates     # (a host-side counter: put back with the buffer)
+            if sched is not None:
+                sched.set_mirror(sched_mirror)   # (the same for the schedule's host mirror)
             del saved
             for net in (st.T, st.F):
                 if hasattr(net, "repack"):
@@ -360,7 +369,9 @@ class PlannedMinimax:
         ent["a"].copy_(alpha, non_blocking=True)
         ent["plan"].replay()
         if st.ema is not None:
-            st.ema.updates += 1                  # the replayed rcot_ema_step launch (the decay is a constant by-value argument)
+            st.ema.updates += 1                  # the replayed rcot_ema_step / rcot_ema_step_dev launch
+        if getattr(st, "schedule", None) is not None:
+            st.schedule.count()                  # the replayed rcot_sched_advance launch: the host mirror follows
         st.logs = ent["logs"]
         return ent["out"]
 

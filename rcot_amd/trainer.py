@@ -6,7 +6,9 @@ structure (critic step -> separate gradient-penalty step -> generator step, :262
 (HIP kernels); this file only sequences it.  Additions are supersets: ``--seed``, ``--synthetic``,
 ``--iters``, data-parallel launch through torchrun (one process per GPU, RCCL), ``--ema`` / ``--val_weights`` (an exponential
 moving average of the transport map's weights: validated, saved next to the raw weights; rcot_amd/ema.py), ``--clip_grad_norm`` /
-``--clip_grad_norm_F`` (gradient-norm clipping and a skip of steps with non-finite gradients, decided on the device: FlatOptimizer).
+``--clip_grad_norm_F`` (gradient-norm clipping and a skip of steps with non-finite gradients, decided on the device: FlatOptimizer),
+``--lr_schedule`` / ``--warmup_iters`` (per-iteration learning-rate schedules, the reference's util/schedulers.py as a table on the device:
+rcot_amd/schedule.py), ``--optimizer AdamW`` with ``--weight_decay`` / ``--weight_decay_F`` and ``--ema_warmup``.
 """
 from __future__ import annotations
 
@@ -104,6 +106,20 @@ parser.add_argument("--clip_grad_norm", type=float, default=0.0,
                          "both decided on the device; inf = skip only.  0 = off, everything as before")
 parser.add_argument("--clip_grad_norm_F", type=float, default=0.0,
                     help="the same for the potential, on both of its steps (critic and gradient penalty), each with its own norm")
+parser.add_argument("--lr_schedule", type=str, default="step",
+                    help="the learning rate per ITERATION (rcot_amd/schedule.py): step (default) = the reference's epoch decay, untouched; const | "
+                         "cosine[:<eta_min>] | linear | restarts:<p1>,<p2>,...[:<w1>,...][:<e1>,...] | multistep:<m1>,<m2>,...[:<gamma>] = the "
+                         "reference's util/schedulers.py, periods and milestones in iterations.  The rates live in a table on the device; one "
+                         "launch per iteration hands them to the optimizers, which are then guarded ones (max_norm inf unless --clip_grad_norm* "
+                         "says otherwise); --step is ignored")
+parser.add_argument("--warmup_iters", type=int, default=0,
+                    help="with a per-iteration --lr_schedule: lr * t / N for the first N iterations, then the schedule over the remaining ones")
+parser.add_argument("--weight_decay", type=float, default=0.01,
+                    help="--optimizer AdamW: the decoupled weight decay of both networks (torch.optim.AdamW's default; the Restormer recipe "
+                         "uses 1e-4)")
+parser.add_argument("--weight_decay_F", type=float, default=None, help="--optimizer AdamW: the potential's weight decay, when it differs")
+parser.add_argument("--ema_warmup", action="store_true",
+                    help="with --ema D: update u of the average uses the decay min(D, (1 + u) / (10 + u)), formed on the device")
 parser.add_argument("--synthetic", action="store_true", help="seeded synthetic patches (no dataset folders needed)")
 parser.add_argument("--iters", type=int, default=20, help="iterations per epoch with --synthetic")
 
@@ -171,6 +187,44 @@ def check_clip_flags(o, stock_mprnet: bool = False) -> None:
                              "GPU visible, or RCOT_MPRNET_STOCK=1) has none")
 
 
+def check_schedule_flags(o, stock_mprnet: bool = False) -> None:
+    """--lr_schedule (grammar: rcot_amd/schedule.py), --warmup_iters, --optimizer AdamW with --weight_decay / --weight_decay_F and
+    --ema_warmup: a malformed spec (the message names the piece), a negative number, --warmup_iters without a per-iteration schedule,
+    --ema_warmup without --ema, and any of them on the stock-ops MPRNet loop are refused up front with SystemExit naming the flag."""
+    from . import schedule
+    try:
+        kind = schedule.parse(o.lr_schedule)["kind"]
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if o.warmup_iters < 0:
+        raise SystemExit(f"--warmup_iters {o.warmup_iters}: the warm-up cannot be negative")
+    if o.warmup_iters > 0 and kind == "step":
+        raise SystemExit(f"--warmup_iters {o.warmup_iters} warms up a per-iteration schedule: it needs --lr_schedule other than step")
+    if o.ema_warmup and o.ema == 0.0:
+        raise SystemExit("--ema_warmup warms up the decay of the weight average: it needs --ema D")
+    for flag in ("weight_decay", "weight_decay_F"):
+        v = getattr(o, flag)
+        if v is not None and not v >= 0.0:                                  # refuses NaN too
+            raise SystemExit(f"--{flag} {v}: the weight decay must be >= 0")
+    if stock_mprnet:
+        used = [f for f, on in (("--lr_schedule", kind != "step"), ("--optimizer AdamW", o.optimizer == "AdamW"), ("--ema_warmup", o.ema_warmup)) if on]
+        if used:
+            raise SystemExit(f"{used[0]} needs the fused optimizers over a flat parameter store: --backbone mprnet on stock PyTorch ops (no "
+                             "GPU visible, or RCOT_MPRNET_STOCK=1) has none")
+
+
+def restore_schedule(sched, state, epochs_done: int, iters_per_epoch: int, ema_updates: Optional[int] = None) -> Optional[str]:
+    """a resumed run's schedule: continue at the checkpoint's stored counters (``state``, its "schedule" entry), or — a checkpoint
+    written without a schedule — start at iteration epochs_done * iters_per_epoch, with the EMA warm-up at the average's own update
+    count; then the line to print is returned"""
+    if state is not None:
+        sched.load_state_dict(state)
+        return None
+    t = int(epochs_done) * int(iters_per_epoch)
+    sched.start_at(t, ema_updates)
+    return f"holds no schedule state (\"schedule\"): the schedule starts at iteration {t} = {epochs_done} epochs of {iters_per_epoch} iterations"
+
+
 def guard_report(name: str, now: dict, before: Optional[dict]) -> str:
     """the per-epoch line of a guarded optimizer from its counters (``now``) and those at the start of the epoch (``before``).  Raises
     SystemExit when the epoch made decisions and every one of them was a skip: the run is not training any more."""
@@ -215,17 +269,24 @@ def unfreeze(model):    # utils.py:28-31
 
 # ------------------------------------------------------------------------------- optimizer
 class FlatOptimizer:
-    """RMSprop / Adam with torch defaults over a network's flat buffers (one fused launch)."""
+    """RMSprop / Adam / AdamW with torch defaults over a network's flat buffers (one fused launch).  ``weight_decay``: AdamW's
+    decoupled decay (ignored by the other two)."""
 
-    def __init__(self, net, kind: str, lr: float, max_norm: Optional[float] = None):
+    def __init__(self, net, kind: str, lr: float, max_norm: Optional[float] = None, weight_decay: float = 0.0):
         self.net, self.kind, self.lr = net, kind, lr
+        self.weight_decay = float(weight_decay) if kind == "AdamW" else 0.0
+        if not self.weight_decay >= 0.0:
+            raise ValueError(f"weight_decay {weight_decay}: the weight decay must be >= 0")
+        #: set by rcot_amd.schedule.Schedule.bind: the rate word of the control block is written by the schedule's advance launch on the
+        #: device, once per iteration, and sync_lr leaves it alone; param_groups[0]["lr"] follows the schedule's host mirror
+        self.scheduled = False
         st = net.store
         be = net.be
         self.param_groups = [{"lr": lr}]          # the reference pokes param_groups[...]["lr"] (:240-243)
         n = st.layout.n_total
         if kind == "RMSprop":
             self.sq = be.zeros(n)
-        elif kind == "Adam":
+        elif kind in ("Adam", "AdamW"):
             self.m, self.v = be.zeros(n), be.zeros(n)
             self.t_main, self.t_tail = 0, 0
         else:
@@ -247,7 +308,7 @@ class FlatOptimizer:
         """Guarded steps read their learning rate from the control block: bring it to ``param_groups[0]["lr"]`` by a stream-ordered
         write when the two differ.  Called before every iteration, eager or replayed, and never recorded into a launch plan (a plan
         records library launches only)."""
-        if self.ctrl is None:
+        if self.ctrl is None or self.scheduled:
             return
         lr = float(self.param_groups[0]["lr"])
         if lr != self._lr_written:
@@ -272,13 +333,25 @@ class FlatOptimizer:
             be.rmsprop_step(st.flat, st.grad, self.sq, n4, lr)
         else:
             self.t_main += 1
-            be.adam_step(st.flat, st.grad, self.m, self.v, min(n4, self._tail_start()), lr, self.t_main)
+            self._adam(st.flat, st.grad, self.m, self.v, min(n4, self._tail_start()), lr, self.t_main)
             if n >= full and self._tail_start() < full:
                 self.t_tail += 1
                 o = self._tail_start()
-                be.adam_step(st.flat[o:], st.grad[o:], self.m[o:], self.v[o:], st.layout.n_total - o, lr, self.t_tail)
+                self._adam(st.flat[o:], st.grad[o:], self.m[o:], self.v[o:], st.layout.n_total - o, lr, self.t_tail)
         if hasattr(self.net, "repack"):
             self.net.repack()            # private K-major weight copies follow the parameters
+
+    def _adam(self, p, g, m, v, n, lr, t):
+        if self.kind == "AdamW":
+            self.net.be.adamw_step(p, g, m, v, n, lr, t, self.weight_decay)
+        else:
+            self.net.be.adam_step(p, g, m, v, n, lr, t)
+
+    def _adam_guarded(self, p, g, m, v, n, counter):
+        if self.kind == "AdamW":
+            self.net.be.adamw_step_guarded(p, g, m, v, n, self.ctrl, counter, self.weight_decay)
+        else:
+            self.net.be.adam_step_guarded(p, g, m, v, n, self.ctrl, counter)
 
     def _step_guarded(self, n, n4, full, same_batch=False):
         """the same ranges as the plain step, behind one decision: the norm is that of grad[0:n4), the range stepped over (in the
@@ -294,9 +367,9 @@ class FlatOptimizer:
         o = self._tail_start()
         tail = n >= full and o < full
         be.grad_decide(self.partials, parts, self.ctrl, adam_mask=3 if tail else 1, inherit=same_batch)      # the counts advance on the device, unless skipped
-        be.adam_step_guarded(st.flat, st.grad, self.m, self.v, min(n4, o), self.ctrl, 0)
+        self._adam_guarded(st.flat, st.grad, self.m, self.v, min(n4, o), 0)
         if tail:
-            be.adam_step_guarded(st.flat[o:], st.grad[o:], self.m[o:], self.v[o:], st.layout.n_total - o, self.ctrl, 1)
+            self._adam_guarded(st.flat[o:], st.grad[o:], self.m[o:], self.v[o:], st.layout.n_total - o, 1)
 
     def guard_counters(self):
         """{max_norm, steps, clipped, skipped, max_seen, last_norm, last_scale} read from the control block (one device read)"""
@@ -323,12 +396,14 @@ class FlatOptimizer:
         if self.ctrl is not None:
             g = self.guard_counters()
             guard = {k: g[k] for k in ("max_norm", "steps", "clipped", "skipped", "max_seen")}
-            if self.kind == "Adam":
+            if self.kind in ("Adam", "AdamW"):
                 t = self.ctrl.cpu().view(torch.int64)
                 t_main, t_tail = int(t[_lib.CB_T]), int(t[_lib.CB_T + 1])
         out = {"kind": self.kind, "lr": self.param_groups[0]["lr"], "t_main": t_main, "t_tail": t_tail, "state": {}}
         if guard is not None:
             out["guard"] = guard
+        if self.kind == "AdamW":
+            out["weight_decay"] = self.weight_decay
         for key, flat in self._state_tensors().items():
             d = {}
             for name, shp in st.shapes:
@@ -349,7 +424,7 @@ class FlatOptimizer:
                 o = st.layout.offset[name]
                 t = sd["state"][key][name]
                 flat[o:o + t.numel()].copy_(t.reshape(-1).to(flat.dtype))
-        if self.kind == "Adam":
+        if self.kind in ("Adam", "AdamW"):
             self.t_main, self.t_tail = int(sd.get("t_main", 0)), int(sd.get("t_tail", 0))
         if self.ctrl is not None:
             # the counters continue (this run's own max_norm stays); Adam's step counts go into the block: the decision that advances
@@ -374,9 +449,11 @@ class FlatOptimizer:
                 t.zero_()
 
 
-def make_optimizers(Tnet, Fnet, name: str, lr: float, max_norm_T: Optional[float] = None, max_norm_F: Optional[float] = None):
-    """trainer.py:121-126: lr/2 for the transport map, lr for the potential.  ``max_norm_*``: guarded steps (FlatOptimizer)."""
-    return FlatOptimizer(Tnet, name, lr / 2, max_norm_T), FlatOptimizer(Fnet, name, lr, max_norm_F)
+def make_optimizers(Tnet, Fnet, name: str, lr: float, max_norm_T: Optional[float] = None, max_norm_F: Optional[float] = None,
+                    weight_decay_T: float = 0.0, weight_decay_F: float = 0.0):
+    """trainer.py:121-126: lr/2 for the transport map, lr for the potential.  ``max_norm_*``: guarded steps (FlatOptimizer);
+    ``weight_decay_*``: AdamW's decay."""
+    return FlatOptimizer(Tnet, name, lr / 2, max_norm_T, weight_decay_T), FlatOptimizer(Fnet, name, lr, max_norm_F, weight_decay_F)
 
 
 # ------------------------------------------------------------------------------- one minimax iteration
@@ -384,8 +461,12 @@ class MinimaxStep:
     """The body of the reference's training loop (trainer.py:247-346) for one (local) batch."""
 
     def __init__(self, Tnet: T_net, Fnet: F_net, T_opt: FlatOptimizer, F_opt: FlatOptimizer, sigma: float,
-                 Sigma: float, bucket_elems: int = 8 << 20, ema=None):
+                 Sigma: float, bucket_elems: int = 8 << 20, ema=None, schedule=None):
         self.T, self.F, self.To, self.Fo = Tnet, Fnet, T_opt, F_opt
+        #: optional rcot_amd.schedule.Schedule (bound to the two optimizers): its advance launch is the first launch of every iteration —
+        #: this iteration's rates into the optimizers' control blocks, the EMA warm-up's 1 - D_u into its block — recorded into the plan
+        #: like any launch; it runs whether or not a step is skipped afterwards, like scheduler.step()
+        self.schedule = schedule
         #: optional rcot_amd.ema.WeightAverage of the transport map: one update per iteration, right after its optimizer step (the
         #: potential is not averaged: it is never used at inference)
         self.ema = ema
@@ -413,7 +494,9 @@ class MinimaxStep:
     def run(self, degraded, target, de_id, alpha, paired: bool):
         """One minimax iteration: replay of the recorded launch plan when available, else the eager launch sequence."""
         self.To.sync_lr()                      # guarded optimizers read their learning rate from a device word: written here, never recorded
-        self.Fo.sync_lr()
+        self.Fo.sync_lr()                      # (scheduled ones: written by the schedule's own launch, the first of the iteration)
+        if self.schedule is not None:
+            self.schedule.show()               # param_groups[0]["lr"] <- this iteration's rate, from the host mirror
         if self.planned is not None and self.grad_probe is None and self.comm_log is None:
             return self.planned.iteration(degraded, target, de_id, alpha, paired)
         return self.iteration(degraded, target, de_id, alpha, paired)
@@ -424,6 +507,8 @@ class MinimaxStep:
         be, T, F = self.be, self.T, self.F
         B = degraded.shape[0]
         Bg = B * self.world
+        if self.schedule is not None:
+            self.schedule.advance(be)                                # once per minimax iteration: all three optimizer steps read its rates
         # The reference evaluates T(degraded) twice per iteration (:271 for the critic, :318 for the generator) with
         # the SAME transport-map parameters (T is only stepped at :346) and the same input: the two results are
         # identical, so it is evaluated once, with the activations the generator backward needs kept resident.
@@ -548,9 +633,13 @@ def adjust_learning_rate(epoch):
 def train(training_data_loader, T_optimizer, F_optimizer, Tnet, Fnet, epoch, stepper: Optional[MinimaxStep] = None):
     """Same signature / behaviour as the reference's train() (trainer.py:234-360).  Batches are
     ([names, de_id], degraded, target) with CPU or device tensors."""
-    lr = adjust_learning_rate(epoch - 1)
-    T_optimizer.param_groups[0]["lr"] = lr / 2
-    F_optimizer.param_groups[0]["lr"] = lr
+    sched = getattr(stepper, "schedule", None)
+    if sched is not None and sched.table is not None:
+        sched.show()                                                       # the rate of the epoch's first iteration; --step plays no part
+    else:
+        lr = adjust_learning_rate(epoch - 1)
+        T_optimizer.param_groups[0]["lr"] = lr / 2
+        F_optimizer.param_groups[0]["lr"] = lr
     if par.rank() == 0:
         print("Epoch={}, lr={}".format(epoch, F_optimizer.param_groups[0]["lr"]))
     st = stepper or MinimaxStep(Tnet, Fnet, T_optimizer, F_optimizer, opt.sigma, opt.Sigma)
@@ -613,13 +702,14 @@ def _as_picklable(net, cls):
     return C.from_state_dict(net.state_dict(), **kw)
 
 
-def save_checkpoint(Tnet, Fnet, epoch, T_optimizer=None, F_optimizer=None, ema=None):
+def save_checkpoint(Tnet, Fnet, epoch, T_optimizer=None, F_optimizer=None, ema=None, schedule=None):
     """trainer.py:362-371: same path pattern and dict keys, and — like the reference — whole network OBJECTS under
     "Tnet"/"Fnet" (class paths ``Net_Restormer.T_net`` / ``F_net``; see rcot_amd/compat.py), so that
     ``torch.load(p)["Tnet"]`` can be called (tester.py:54) and ``.state_dict()`` read (trainer.py:105).  Superset:
     optimizer state under "T_optimizer"/"F_optimizer" (the reference loses RMSprop's square_avg on resume); with ``ema`` (a
     WeightAverage of Tnet) the averaged weights as a plain state_dict under "Tnet_ema" and {"decay", "updates"} under "ema" —
-    "Tnet" stays the raw network, which a resumed run keeps training."""
+    "Tnet" stays the raw network, which a resumed run keeps training.  With ``schedule`` (a rcot_amd.schedule.Schedule) its counters under
+    "schedule": --resume continues at the stored iteration."""
     path = "checkpoint/" + "model_" + str(opt.type) + "_" + "_" + str(opt.nEpochs) + "_" + str(opt.sigma) + ".pth"
     os.makedirs("checkpoint/", exist_ok=True)
     if not hasattr(Tnet, "decoder"):
@@ -635,6 +725,8 @@ def save_checkpoint(Tnet, Fnet, epoch, T_optimizer=None, F_optimizer=None, ema=N
     if ema is not None:
         state["Tnet_ema"] = ema.tensors()
         state["ema"] = {"decay": ema.decay, "updates": ema.updates}
+    if schedule is not None:
+        state["schedule"] = schedule.state_dict()
     torch.save(state, path)
     print("Checkpoint saved to {}".format(path))
     return path
@@ -826,6 +918,7 @@ def main(argv=None):
     hip_mprnet = opt.backbone == "mprnet" and torch.cuda.is_available() and os.environ.get("RCOT_MPRNET_STOCK", "0") != "1"
     check_ema_flags(opt, stock_mprnet=opt.backbone == "mprnet" and not hip_mprnet)
     check_clip_flags(opt, stock_mprnet=opt.backbone == "mprnet" and not hip_mprnet)
+    check_schedule_flags(opt, stock_mprnet=opt.backbone == "mprnet" and not hip_mprnet)
     if opt.backbone == "mprnet" and not hip_mprnet:
         return main_mprnet()
     if "RANK" in os.environ and "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) > 1:
@@ -860,7 +953,22 @@ def main(argv=None):
     else:
         Tnet = _make_net("T_net", decoder=True, seed=seed)                 # trainer.py:92
     Fnet = _make_net("F_net", patch_size=opt.patch_size, seed=seed + 1)    # :93
-    T_opt, F_opt = make_optimizers(Tnet, Fnet, opt.optimizer, opt.lr, opt.clip_grad_norm or None, opt.clip_grad_norm_F or None)
+    from . import schedule as _schedule
+    scheduled = _schedule.parse(opt.lr_schedule)["kind"] != "step"
+    max_T, max_F = opt.clip_grad_norm or None, opt.clip_grad_norm_F or None
+    if scheduled:
+        # a scheduled optimizer reads its rate from a control block, which only the guarded step kernels do: guard only where no cap was asked for
+        unguarded = [n for n, m in (("T_net", max_T), ("F_net", max_F)) if m is None]
+        max_T, max_F = max_T or math.inf, max_F or math.inf
+        if rank == 0:
+            if unguarded:
+                print(f"--lr_schedule {opt.lr_schedule}: the optimizer steps of {' and '.join(unguarded)} are guarded steps with max_norm inf "
+                      "(steps with non-finite gradients are skipped; nothing is clipped)")
+            if opt.step != parser.get_default("step"):
+                print(f"--lr_schedule {opt.lr_schedule}: --step {opt.step} is ignored (it belongs to the epoch decay of --lr_schedule step)")
+    wd_T = opt.weight_decay
+    wd_F = opt.weight_decay if opt.weight_decay_F is None else opt.weight_decay_F
+    T_opt, F_opt = make_optimizers(Tnet, Fnet, opt.optimizer, opt.lr, max_T, max_F, wd_T, wd_F)
     from .compat import load_checkpoint
     ck = None
     if opt.resume:
@@ -905,6 +1013,8 @@ def main(argv=None):
         avg.broadcast()
     elif has_avg and rank == 0:
         print(f"=> '{opt.resume}' holds a weight average (\"Tnet_ema\"): ignored without --ema")
+    sched_state = ck.get("schedule") if isinstance(ck, dict) else None
+    resumed = ck is not None
     ck = None
     if opt.synthetic:
         from .synth import SyntheticLoader
@@ -919,7 +1029,24 @@ def main(argv=None):
         loader = FolderLoader(opt, opt.batchSize // world, seed=seed, rank=rank, world=world, threads=opt.threads, cache=cache)
     import glob
     deg_list, tar_list = sorted(glob.glob(opt.degset + "*")), sorted(glob.glob(opt.tarset + "*"))   # :137-141
-    stepper = MinimaxStep(Tnet, Fnet, T_opt, F_opt, opt.sigma, opt.Sigma, ema=avg)
+    # the per-iteration schedule and / or the EMA warm-up: one block on the device per rank, every rank advances its own identical one
+    sched = None
+    if scheduled or opt.ema_warmup:
+        total = opt.nEpochs * len(loader)
+        try:
+            sched = _schedule.Schedule(default_backend(), opt.lr_schedule, opt.lr, max(total, 1), opt.warmup_iters,
+                                       ema_decay=opt.ema if opt.ema_warmup else 0.0)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        sched.bind(T_opt, F_opt)
+        if resumed:
+            note = restore_schedule(sched, sched_state, opt.start_epoch - 1, len(loader), avg.updates if avg is not None else None)
+            if note and rank == 0:
+                print(f"=> '{opt.resume}' {note}")
+        sched.broadcast()
+        if opt.ema_warmup:
+            avg.omd_word = sched.omd_word
+    stepper = MinimaxStep(Tnet, Fnet, T_opt, F_opt, opt.sigma, opt.Sigma, ema=avg, schedule=sched)
     stepper.sample_dir = "./checksample/" + str(opt.type) + "/" if rank == 0 else None
     TLOSS, PLOSS = [], []
     guarded = [(name, o) for name, o in (("T_net", T_opt), ("F_net", F_opt)) if o.ctrl is not None]
@@ -959,7 +1086,7 @@ def main(argv=None):
                 scio.savemat('PLOSSrain.mat', {'PLOSS': PLOSS})
             except ImportError:
                 pass
-            save_checkpoint(Tnet, Fnet, epoch, T_opt, F_opt, avg)          # :165 (mprnet backbone: the state_dict form)
+            save_checkpoint(Tnet, Fnet, epoch, T_opt, F_opt, avg, sched)          # :165 (mprnet backbone: the state_dict form)
         if world > 1:
             torch.distributed.barrier()
     return Tnet, Fnet
