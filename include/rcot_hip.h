@@ -25,7 +25,7 @@ extern "C" {
 
 /* Bumped on EVERY signature change; returned by rcot_abi_version() (csrc/api.hip) and compared by the loader
  * (rcot_amd/lib.py ABI_VERSION, tests/test_abi.py) so that a stale prebuilt .so is refused, not mis-called. */
-#define RCOT_ABI_VERSION 40
+#define RCOT_ABI_VERSION 41
 
 /* Arithmetic of the MFMA products of the three GEMM-shaped entry points that take `prec` (rcot_gemm_kmajor,
  * rcot_conv1x1_wgrad, rcot_bmm_nt); operands and results are fp32 in memory either way.
@@ -595,6 +595,25 @@ int rcot_pad2d(const float* src, float* dst, long planes, int h, int w, int Hp, 
 int rcot_image_egress(const float* restored, const float* degraded, const unsigned char* target, int h, int w, int Hp, int Wp,
                       float res_scale, unsigned char* out_u8, unsigned char* res_u8, double* stats, float* ws, size_t ws_bytes,
                       void* stream);
+/* The two image entry points for N images of one PADDED shape in one launch each (rcot_amd/valsuite.py: the images of a validation set
+ * that pad to the same Hp x Wp).  `table` is a DEVICE array of N rows of 4 int64, trusted as rcot_patch_prep_batch's is: the CALLER
+ * checks every row on the host before it launches (HipBackend.image_ingest_batch / image_egress_batch do).
+ *  rcot_image_ingest_batch : row { img, h, w, 0 }, img uint8 [h][w][3] at ANY byte address; out float [N][3][Hp][Wp].  Slot i holds the
+ *                            bits rcot_image_ingest(img_i, h_i, w_i, out + i 3 Hp Wp, Hp, Wp, mode) gives.  The rows may differ in
+ *                            (h, w) as long as `mode` pads each to Hp x Wp.  One launch.  RCOT_EINVAL without a launch for a null
+ *                            pointer, N < 1, N > 65535, an unknown mode, Hp or Wp < 1.
+ *  rcot_image_egress_batch : restored float [N][3][Hp][Wp]; row { target, out_u8 (0: none), h, w }, both uint8 [h][w][3] at any byte
+ *                            address; stats double [N][4] (8-byte aligned), or null when every row has an out_u8 (target is not read
+ *                            then).  Row i gives, bit for bit, the out_u8 and the four stats of rcot_image_egress(restored_i, NULL,
+ *                            target_i, h_i, w_i, Hp, Wp, ...); there is no residual image.  Two launches, one without statistics; no
+ *                            atomics: every image sums the partials of its OWN grid of 4-row x 256-column workgroups in the single
+ *                            kernel's order, whatever the launch grid (sized by Hp x Wp) is.  ws needs
+ *                            24 N ceil(Hp / 4) ceil(Wp / 256) bytes, 8-byte aligned; smaller or misaligned: RCOT_EWORKSPACE, nothing
+ *                            is launched and stats is untouched.  RCOT_EINVAL without a launch for a null restored or table, N < 1,
+ *                            N > 65535, Hp or Wp < 1, a misaligned stats. */
+int rcot_image_ingest_batch(const long long* table, int N, int Hp, int Wp, int mode, float* out, void* stream);
+int rcot_image_egress_batch(const float* restored, const long long* table, int N, int Hp, int Wp, double* stats, float* ws,
+                            size_t ws_bytes, void* stream);
 
 /* ---- standard image-quality figures (csrc/quality.hip; rcot_amd/quality.py, the testers' --ssim_window / --color) --------------------
  * The two published SSIM protocols and PSNR, in RGB or on the Y channel, between two uint8 [h][w][3] (HWC, device) images a and b — the

@@ -3,6 +3,8 @@
 //   rcot_pad2d        : the same padding for float planes (the testers' noisy input, batched tensors)
 //   rcot_image_egress : crop of the network's output, 8-bit quantisation as torchvision's save_image does it, the scaled residual, and the
 //                       sums under PSNR (float and 8-bit) and under the testers' 2 x 2 box-window SSIM
+//   rcot_image_ingest_batch / rcot_image_egress_batch : the same for N images of one padded shape in one launch (two with statistics), from
+//                       a device table of one row per image (rcot_amd/valsuite.py); the device code is the single kernels', so are the bits
 // All of it is HBM-bound row work.  One wave owns TILE pixels of one image row (4 per lane: float4 on the planes where the row length
 // and the pointers allow); the 3w-byte HWC rows are generally unaligned, so their bytes cross LDS: aligned dwords on the global side,
 // single bytes only for a row segment's first / last partial dword.  The statistics are per-workgroup partials in the caller's
@@ -21,7 +23,7 @@ constexpr int LW = (4 + 3 + 3 * (TILE + 1) + 3) / 4 + 1;   // LDS words of one s
 // source row / column of padded row / column r of an n-long axis: torch's 'reflect' (mode 1) or 'replicate' (mode 2)
 __device__ __forceinline__ int src_index(int r, int n, int mode) { return r < n ? r : (mode == 1 ? 2 * (n - 1) - r : n - 1); }
 
-inline bool pad_geometry_ok(int h, int w, int Hp, int Wp, int mode) {
+__host__ __device__ inline bool pad_geometry_ok(int h, int w, int Hp, int Wp, int mode) {
     if (h <= 0 || w <= 0 || Hp < h || Wp < w) return false;
     if (mode == 0) return Hp == h && Wp == w;
     if (mode == 1) return Hp - h <= h - 1 && Wp - w <= w - 1;
@@ -67,9 +69,10 @@ __device__ __forceinline__ void stage_out(uint8_t* __restrict__ g, int n, const 
 
 // ------------------------------------------------------------------ ingest: uint8 [h][w][3] -> float [3][Hp][Wp] / 255, padded
 // VEC: Wp % 4 == 0 and `out` 16-byte aligned (every lane's four pixels are inside the row)
+// The workgroup's part of one image: rows blockIdx.x * ROWS .., columns blockIdx.y * TILE .. (shared by the single and the batched kernel)
 template <bool VEC>
-__global__ __launch_bounds__(256) void ingest_kernel(const uint8_t* __restrict__ img, float* __restrict__ out, int h, int w, int Hp, int Wp,
-                                                     int mode) {
+__device__ __forceinline__ void ingest_tile(const uint8_t* __restrict__ img, float* __restrict__ out, int h, int w, int Hp, int Wp,
+                                            int mode) {
     __shared__ uint32_t sm[ROWS][LW];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int y = blockIdx.x * ROWS + wave, x0 = blockIdx.y * TILE;
@@ -106,6 +109,24 @@ __global__ __launch_bounds__(256) void ingest_kernel(const uint8_t* __restrict__
                 if (x + k < Wp) o[k] = v[k];
         }
     }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void ingest_kernel(const uint8_t* __restrict__ img, float* __restrict__ out, int h, int w, int Hp, int Wp,
+                                                     int mode) {
+    ingest_tile<VEC>(img, out, h, w, Hp, Wp, mode);
+}
+
+// image blockIdx.z of a batch: row {img, h, w, 0} of the table, slot blockIdx.z of out [N][3][Hp][Wp].  The caller has checked every row;
+// a row whose geometry `mode` cannot pad is left out all the same (its reads would leave the image).
+template <bool VEC>
+__global__ __launch_bounds__(256) void ingest_batch_kernel(const long long* __restrict__ table, float* __restrict__ out, int Hp, int Wp,
+                                                           int mode) {
+    const long long* row = table + 4 * (long)blockIdx.z;
+    const uint8_t* img = reinterpret_cast<const uint8_t*>(row[0]);
+    const int h = (int)row[1], w = (int)row[2];
+    if (!img || !pad_geometry_ok(h, w, Hp, Wp, mode)) return;
+    ingest_tile<VEC>(img, out + (long)blockIdx.z * 3 * Hp * Wp, h, w, Hp, Wp, mode);
 }
 
 // ------------------------------------------------------------------ pad2d: float [planes][h][w] -> [planes][Hp][Wp]
@@ -177,8 +198,10 @@ __device__ __forceinline__ void load4(const float* __restrict__ p, const EgressA
 
 // One wave per TILE pixels of image row y.  LDS per wave: the quantised rows y (0) and y - 1 (1) and the target's, each with the pixel left
 // of the segment (the 2 x 2 SSIM window ends at (y, x)), and the residual row.  Row y - 1 is re-quantised from `restored` (an L2 hit).
+// `gx`: workgroups along the rows of THIS image's own grid (ceil(h / ROWS)), `nb`: workgroups of that grid — the partials are laid out by
+// them, whatever the launch grid is (the batched launch is sized by the padded shape).
 template <bool VEC>
-__global__ __launch_bounds__(256) void egress_kernel(EgressArgs a) {
+__device__ __forceinline__ void egress_tile(const EgressArgs& a, long gx, long nb) {
     __shared__ uint32_t s_q[ROWS][2][LW], s_t[ROWS][2][LW], s_r[ROWS][LW];
     __shared__ double s_d[ROWS][2];
     __shared__ long long s_i[ROWS];
@@ -297,7 +320,7 @@ __global__ __launch_bounds__(256) void egress_kernel(EgressArgs a) {
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const long nb = (long)gridDim.x * gridDim.y, b = (long)blockIdx.y * gridDim.x + blockIdx.x;
+        const long b = (long)blockIdx.y * gx + blockIdx.x;
         double f = 0.0, s = 0.0;
         long long n = 0;
 #pragma unroll
@@ -312,9 +335,44 @@ __global__ __launch_bounds__(256) void egress_kernel(EgressArgs a) {
     }
 }
 
+template <bool VEC>
+__global__ __launch_bounds__(256) void egress_kernel(EgressArgs a) {
+    egress_tile<VEC>(a, gridDim.x, (long)gridDim.x * gridDim.y);
+}
+
+// The batched form.  Image i = blockIdx.z: row {target, out_u8 (0: none), h, w} of the table, slot i of restored [N][3][Hp][Wp].  The launch
+// grid covers Hp x Wp; the workgroups beyond an image's own grid leave at once.  Image i owns `slot` = 3 * ceil(Hp / ROWS) * ceil(Wp / TILE)
+// 8-byte words of the workspace and lays its partials out there as the single kernel does: by its own grid.
+__device__ __forceinline__ long own_grid(int h, int w, long& gx) {
+    gx = (h + ROWS - 1) / ROWS;
+    return gx * ((w + TILE - 1) / TILE);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void egress_batch_kernel(const float* __restrict__ restored, const long long* __restrict__ table, int Hp,
+                                                           int Wp, double* __restrict__ ws, long slot) {
+    const long i = blockIdx.z;
+    const long long* row = table + 4 * i;
+    EgressArgs a;
+    a.h = (int)row[2]; a.w = (int)row[3]; a.Hp = Hp; a.Wp = Wp;
+    if (a.h <= 0 || a.w <= 0 || a.h > Hp || a.w > Wp) return;             // (checked by the caller; never reached with a checked table)
+    long gx;
+    const long nb = own_grid(a.h, a.w, gx);
+    if ((long)blockIdx.x >= gx || (long)blockIdx.y * TILE >= a.w) return;
+    a.restored = restored + i * 3 * Hp * Wp;
+    a.degraded = nullptr;
+    a.target = reinterpret_cast<const uint8_t*>(row[0]);
+    a.out_u8 = reinterpret_cast<uint8_t*>(row[1]);
+    a.res_u8 = nullptr;
+    a.res_scale = 0.f;
+    a.part_d = ws && a.target ? ws + i * slot : nullptr;
+    a.part_i = a.part_d ? reinterpret_cast<long long*>(a.part_d) + 2 * nb : nullptr;
+    egress_tile<VEC>(a, gx, nb);
+}
+
 // stats[0..4) from the partials, one workgroup, fixed order (final_sums)
-__global__ __launch_bounds__(256) void egress_final_kernel(const double* __restrict__ part_d, const long long* __restrict__ part_i, long nb,
-                                                           int h, int w, double* __restrict__ stats) {
+__device__ __forceinline__ void egress_final(const double* __restrict__ part_d, const long long* __restrict__ part_i, long nb, int h, int w,
+                                             double* __restrict__ stats) {
     double d[2];
     long long n;
     final_sums<2>(part_d, part_i, nb, d, n);
@@ -324,6 +382,24 @@ __global__ __launch_bounds__(256) void egress_final_kernel(const double* __restr
         stats[2] = d[1];
         stats[3] = 3.0 * (double)(h > 10 ? h - 10 : 0) * (double)(w > 10 ? w - 10 : 0);
     }
+}
+
+__global__ __launch_bounds__(256) void egress_final_kernel(const double* __restrict__ part_d, const long long* __restrict__ part_i, long nb,
+                                                           int h, int w, double* __restrict__ stats) {
+    egress_final(part_d, part_i, nb, h, w, stats);
+}
+
+// one workgroup per image of the batch: stats [N][4]
+__global__ __launch_bounds__(256) void egress_batch_final_kernel(const long long* __restrict__ table, int Hp, int Wp,
+                                                                 const double* __restrict__ ws, long slot, double* __restrict__ stats) {
+    const long i = blockIdx.x;
+    const long long* row = table + 4 * i;
+    const int h = (int)row[2], w = (int)row[3];
+    if (!row[0] || h <= 0 || w <= 0 || h > Hp || w > Wp) return;
+    long gx;
+    const long nb = own_grid(h, w, gx);
+    const double* part_d = ws + i * slot;
+    egress_final(part_d, reinterpret_cast<const long long*>(part_d) + 2 * nb, nb, h, w, stats + 4 * i);
 }
 
 }  // namespace
@@ -338,6 +414,18 @@ int rcot_image_ingest(const unsigned char* img, int h, int w, float* out, int Hp
         RCOT_LAUNCH(ingest_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, img, out, h, w, Hp, Wp, mode);
     else
         RCOT_LAUNCH(ingest_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, img, out, h, w, Hp, Wp, mode);
+    RCOT_LAUNCH_CHECK();
+    return RCOT_OK;
+}
+
+int rcot_image_ingest_batch(const long long* table, int N, int Hp, int Wp, int mode, float* out, void* stream) {
+    if (!table || !out || N < 1 || N > 65535 || mode < 0 || mode > 2 || Hp < 1 || Wp < 1) return RCOT_EINVAL;
+    const dim3 grid(cdiv(Hp, ROWS), cdiv(Wp, TILE), N);
+    if (grid.y > 65535u) return RCOT_EINVAL;
+    if ((Wp & 3) == 0 && al16(out))                       // (every slot is 12 Hp Wp bytes behind the one before: aligned alike)
+        RCOT_LAUNCH(ingest_batch_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, table, out, Hp, Wp, mode);
+    else
+        RCOT_LAUNCH(ingest_batch_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, table, out, Hp, Wp, mode);
     RCOT_LAUNCH_CHECK();
     return RCOT_OK;
 }
@@ -385,6 +473,27 @@ int rcot_image_egress(const float* restored, const float* degraded, const unsign
     if (stats) {
         RCOT_LAUNCH(egress_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)a.part_d, (const long long*)a.part_i, nb, h,
                     w, stats);
+        RCOT_LAUNCH_CHECK();
+    }
+    return RCOT_OK;
+}
+
+int rcot_image_egress_batch(const float* restored, const long long* table, int N, int Hp, int Wp, double* stats, float* ws, size_t ws_bytes,
+                            void* stream) {
+    if (!restored || !table || N < 1 || N > 65535 || Hp < 1 || Wp < 1) return RCOT_EINVAL;
+    const dim3 grid(cdiv(Hp, ROWS), cdiv(Wp, TILE), N);
+    if (grid.y > 65535u) return RCOT_EINVAL;
+    if (stats && (reinterpret_cast<uintptr_t>(stats) & 7)) return RCOT_EINVAL;
+    const long slot = 3L * grid.x * grid.y;
+    if (stats && (!ws || (reinterpret_cast<uintptr_t>(ws) & 7) || (size_t)N * slot * 8 > ws_bytes)) return RCOT_EWORKSPACE;
+    double* wsd = stats ? reinterpret_cast<double*>(ws) : nullptr;
+    if ((Wp & 3) == 0 && al16(restored))
+        RCOT_LAUNCH(egress_batch_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, restored, table, Hp, Wp, wsd, slot);
+    else
+        RCOT_LAUNCH(egress_batch_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, restored, table, Hp, Wp, wsd, slot);
+    RCOT_LAUNCH_CHECK();
+    if (stats) {
+        RCOT_LAUNCH(egress_batch_final_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, table, Hp, Wp, (const double*)wsd, slot, stats);
         RCOT_LAUNCH_CHECK();
     }
     return RCOT_OK;

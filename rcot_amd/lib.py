@@ -9,7 +9,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 40    # == RCOT_ABI_VERSION in include/rcot_hip.h (checked by tests/test_abi.py and at load time)
+ABI_VERSION = 41    # == RCOT_ABI_VERSION in include/rcot_hip.h (checked by tests/test_abi.py and at load time)
 PREC_FP32, PREC_BF16X3, PREC_BF16X6, PREC_BF16X1 = 0, 1, 2, 3     # RCOT_PREC_* of include/rcot_hip.h
 # the control block of a guarded optimizer (include/rcot_hip.h): word indices into a float64 tensor of CB_WORDS (the I words through .view(int64))
 SUMSQ_MAX_PARTS, CB_WORDS = 4096, 16
@@ -140,6 +140,8 @@ SIGNATURES = {
     "rcot_image_ingest": [_f, _i, _i, _f, _i, _i, _i, _f],
     "rcot_pad2d": [_f, _f, _l, _i, _i, _i, _i, _i, _f],
     "rcot_image_egress": [_f, _f, _f, _i, _i, _i, _i, _fl, _f, _f, _f, _f, _sz, _f],
+    "rcot_image_ingest_batch": [_f, _i, _i, _i, _i, _f, _f],                                   # table: a DEVICE int64 array
+    "rcot_image_egress_batch": [_f, _f, _i, _i, _i, _f, _f, _sz, _f],                          # table: a DEVICE int64 array
     # standard image-quality figures (csrc/quality.hip)
     "rcot_image_quality": [_f, _f, _i, _i, _i, _i, _f, _f, _sz, _f],
     "rcot_image_blockiness": [_f, _f, _i, _i, _i, _i, _i, _f, _f, _sz, _f],                    # stats: a DEVICE int64 array

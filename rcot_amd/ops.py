@@ -61,6 +61,69 @@ def check_patch_rows(rows, P: int, deg_out, clean_out) -> None:
             raise ValueError(f"patch_prep_batch: row {b}: mode {mode} is not one of the dihedral maps 0..7")
 
 
+_PAD_NAMES = ("none", "reflect", "replicate")
+
+
+def _check_u8_row(what: str, i: int, name: str, t, device):
+    if t is None or t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or not t.is_contiguous():
+        raise ValueError(f"{what}: row {i}: the {name} must be a contiguous uint8 [h, w, 3] tensor")
+    if t.device != device:
+        raise ValueError(f"{what}: row {i}: the {name} is on {t.device}, the batch on {device}")
+
+
+def check_ingest_rows(imgs, Hp: int, Wp: int, mode, out, device) -> None:
+    """The host check of ``image_ingest_batch`` (backend-independent: the kernel trusts its table): 1 .. 65535 contiguous uint8
+    [h, w, 3] images on ``device`` that ``mode`` pads to Hp x Wp (``wholeimage.pad_geometry``'s rules), and ``out`` (None: not made
+    yet) a contiguous float32 tensor of N * 3 * Hp * Wp elements there.  Raises ValueError naming the first row that fails."""
+    what = "image_ingest_batch"
+    mode = "none" if mode is None else mode
+    if mode not in _PAD_NAMES:
+        raise ValueError(f"{what}: padding mode {mode!r}: expected one of {_PAD_NAMES}")
+    N, Hp, Wp = len(imgs), int(Hp), int(Wp)
+    if not 1 <= N <= 65535 or Hp < 1 or Wp < 1:
+        raise ValueError(f"{what}: needs 1 .. 65535 rows and a padded shape of at least 1 x 1, got {N} row(s), {Hp} x {Wp}")
+    if out is not None and (out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != N * 3 * Hp * Wp or out.device != device):
+        raise ValueError(f"{what}: out must be a contiguous float32 [{N}, 3, {Hp}, {Wp}] tensor on {device}, got {out.dtype} "
+                         f"{tuple(out.shape)} on {out.device}")
+    for i, t in enumerate(imgs):
+        _check_u8_row(what, i, "image", t, device)
+        h, w = int(t.shape[0]), int(t.shape[1])
+        ok = h >= 1 and w >= 1 and h <= Hp and w <= Wp
+        if mode == "none":
+            ok = ok and (h, w) == (Hp, Wp)
+        elif mode == "reflect":
+            ok = ok and Hp - h <= h - 1 and Wp - w <= w - 1
+        if not ok:
+            raise ValueError(f"{what}: row {i}: {mode} cannot pad {h} x {w} to {Hp} x {Wp}")
+
+
+def check_egress_rows(restored, sizes, targets, wants, want_stats: bool, device) -> None:
+    """The host check of ``image_egress_batch``: ``restored`` a contiguous float32 [N, 3, Hp, Wp] tensor on ``device``, one (h, w)
+    inside Hp x Wp per row, a uint8 [h, w, 3] target per row when statistics are asked for, and something to do for every row (an
+    8-bit output or the statistics).  Raises ValueError naming the first row that fails."""
+    what = "image_egress_batch"
+    N = len(sizes)
+    if not 1 <= N <= 65535:
+        raise ValueError(f"{what}: needs 1 .. 65535 rows, got {N}")
+    if (restored.dtype != torch.float32 or restored.dim() != 4 or not restored.is_contiguous() or restored.shape[0] != N
+            or restored.shape[1] != 3 or restored.device != device):
+        raise ValueError(f"{what}: restored must be a contiguous float32 [{N}, 3, Hp, Wp] tensor on {device}, got {restored.dtype} "
+                         f"{tuple(restored.shape)} on {restored.device}")
+    Hp, Wp = int(restored.shape[2]), int(restored.shape[3])
+    if len(wants) != N or (want_stats and (targets is None or len(targets) != N)):
+        raise ValueError(f"{what}: {N} row(s) need {N} output choices" + (f" and {N} targets" if want_stats else ""))
+    for i, (h, w) in enumerate(sizes):
+        h, w = int(h), int(w)
+        if not (1 <= h <= Hp and 1 <= w <= Wp):
+            raise ValueError(f"{what}: row {i}: {h} x {w} is no crop of the {Hp} x {Wp} planes")
+        if want_stats:
+            _check_u8_row(what, i, "target", targets[i], device)
+            if tuple(targets[i].shape[:2]) != (h, w):
+                raise ValueError(f"{what}: row {i}: the target is {targets[i].shape[0]} x {targets[i].shape[1]}, the crop {h} x {w}")
+        elif not wants[i]:
+            raise ValueError(f"{what}: row {i}: neither an 8-bit output nor statistics were asked for")
+
+
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None) or (lambda i: torch.cuda.current_stream(i).cuda_stream)
 
 
@@ -1449,6 +1512,72 @@ class HipBackend:
                                             h, w, Hp, Wp, float(res_scale), _ptr(out_u8), _ptr(res_u8), _ptr(stats), ws.data_ptr(),
                                             ws.numel() * ws.element_size(), self._st()), "rcot_image_egress")
         return out_u8, res_u8, stats
+
+    def _device_table(self, flat):
+        # (pinned: the copy is asynchronous, and torch's host allocator keeps the block until the copy has run)
+        return torch.tensor(flat, dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
+
+    def image_ingest_batch(self, imgs, Hp: int, Wp: int, mode, out=None):
+        """``imgs``: N uint8 [h, w, 3] images on the device (any byte address: views into an arena of packed images are fine), each of
+        a size ``mode`` pads to Hp x Wp -> float [N, 3, Hp, Wp] in ONE launch, slot i with the bits ``image_ingest`` gives
+        (rcot_image_ingest_batch).  Every row is checked on the host first (``check_ingest_rows``: ValueError, nothing launched); the
+        table travels in one pinned host tensor, one copy on the current stream."""
+        assert self._plan is None
+        if out is None:
+            check_ingest_rows(imgs, Hp, Wp, mode, None, self.device)
+            out = self.empty(len(imgs), 3, Hp, Wp)
+        check_ingest_rows(imgs, Hp, Wp, mode, out, self.device)
+        flat = []
+        for t in imgs:
+            flat += [t.data_ptr(), int(t.shape[0]), int(t.shape[1]), 0]
+        table = self._device_table(flat)
+        _lib.check(self.L.rcot_image_ingest_batch(table.data_ptr(), len(imgs), int(Hp), int(Wp), self.PAD_MODES[mode], out.data_ptr(),
+                                                  self._st()), "rcot_image_ingest_batch")
+        return out
+
+    EGRESS_TILE = (4, 256)                         # ROWS x TILE of csrc/imageio.hip: pixels of one workgroup
+
+    @classmethod
+    def image_egress_batch_ws_bytes(cls, N: int, Hp: int, Wp: int) -> int:
+        """workspace bytes rcot_image_egress_batch needs for statistics (include/rcot_hip.h): 24 per workgroup of the Hp x Wp grid, per image"""
+        th, tw = cls.EGRESS_TILE
+        return 24 * int(N) * (-(-int(Hp) // th)) * (-(-int(Wp) // tw))
+
+    def image_egress_batch(self, restored, sizes, targets=None, want_out=True, want_stats: bool = False, ws=None, outs=None, stats=None):
+        """restored float [N, 3, Hp, Wp]; ``sizes``: N (h, w); ``targets``: N uint8 [h, w, 3] images (needed for statistics) ->
+        (outs, stats): ``outs`` a list of N uint8 [h, w, 3] crops quantised as ``image_egress`` does (``want_out``: a bool, or one bool
+        per image; None where not asked for) and ``stats`` float64 [N, 4] or None — row i bit for bit what ``image_egress`` gives for
+        image i.  Two launches, one without statistics (rcot_image_egress_batch).  The rows are checked on the host first
+        (``check_egress_rows``: ValueError, nothing launched).  ``outs`` (a list of uint8 [h, w, 3] tensors or None per image, at any
+        byte address; replaces ``want_out``) and ``stats`` (float64 [N, 4]): the caller's own tensors instead of new ones."""
+        assert self._plan is None
+        N = len(sizes)
+        if outs is not None:
+            wants = [o is not None for o in outs]
+        else:
+            wants = [bool(want_out)] * N if isinstance(want_out, bool) else [bool(v) for v in want_out]
+        want_stats = want_stats or stats is not None
+        check_egress_rows(restored, sizes, targets, wants, want_stats, self.device)
+        Hp, Wp = int(restored.shape[-2]), int(restored.shape[-1])
+        if outs is None:
+            outs = [torch.empty(h, w, 3, dtype=torch.uint8, device=self.device) if wo else None for (h, w), wo in zip(sizes, wants)]
+        for i, ((h, w), o) in enumerate(zip(sizes, outs)):
+            if o is not None:
+                _check_u8_row("image_egress_batch", i, "8-bit output", o, self.device)
+                if tuple(o.shape[:2]) != (int(h), int(w)):
+                    raise ValueError(f"image_egress_batch: row {i}: the 8-bit output is {o.shape[0]} x {o.shape[1]}, the crop {h} x {w}")
+        flat = []
+        for i, (h, w) in enumerate(sizes):
+            flat += [targets[i].data_ptr() if want_stats else 0, 0 if outs[i] is None else outs[i].data_ptr(), int(h), int(w)]
+        table = self._device_table(flat)
+        ws = self.ws if ws is None else ws
+        if want_stats and stats is None:
+            stats = torch.empty(N, 4, dtype=torch.float64, device=self.device)
+        if stats is not None and (stats.dtype != torch.float64 or not stats.is_contiguous() or stats.numel() != 4 * N or stats.device != self.device):
+            raise ValueError(f"image_egress_batch: stats must be a contiguous float64 [{N}, 4] tensor on {self.device}")
+        _lib.check(self.L.rcot_image_egress_batch(restored.data_ptr(), table.data_ptr(), N, Hp, Wp, _ptr(stats), ws.data_ptr(),
+                                                  ws.numel() * ws.element_size(), self._st()), "rcot_image_egress_batch")
+        return outs, stats
 
     # ------------------------------------------------------------------ views and their blend: tiles, self-ensemble (csrc/views.hip)
     def _view_args(self, img, ys, xs, modes, Th: int, Tw: int, what: str):

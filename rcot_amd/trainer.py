@@ -120,6 +120,9 @@ parser.add_argument("--weight_decay", type=float, default=0.01,
 parser.add_argument("--weight_decay_F", type=float, default=None, help="--optimizer AdamW: the potential's weight decay, when it differs")
 parser.add_argument("--ema_warmup", action="store_true",
                     help="with --ema D: update u of the average uses the decay min(D, (1 + u) / (10 + u)), formed on the device")
+from . import valsuite as _valsuite  # noqa: E402
+
+_valsuite.add_arguments(parser)                # --val_set, --val_batch, --val_cache_gb, --save_best (rcot_amd/valsuite.py)
 parser.add_argument("--synthetic", action="store_true", help="seeded synthetic patches (no dataset folders needed)")
 parser.add_argument("--iters", type=int, default=20, help="iterations per epoch with --synthetic")
 
@@ -702,14 +705,15 @@ def _as_picklable(net, cls):
     return C.from_state_dict(net.state_dict(), **kw)
 
 
-def save_checkpoint(Tnet, Fnet, epoch, T_optimizer=None, F_optimizer=None, ema=None, schedule=None):
+def save_checkpoint(Tnet, Fnet, epoch, T_optimizer=None, F_optimizer=None, ema=None, schedule=None, best=None, is_best=False):
     """trainer.py:362-371: same path pattern and dict keys, and — like the reference — whole network OBJECTS under
     "Tnet"/"Fnet" (class paths ``Net_Restormer.T_net`` / ``F_net``; see rcot_amd/compat.py), so that
     ``torch.load(p)["Tnet"]`` can be called (tester.py:54) and ``.state_dict()`` read (trainer.py:105).  Superset:
     optimizer state under "T_optimizer"/"F_optimizer" (the reference loses RMSprop's square_avg on resume); with ``ema`` (a
     WeightAverage of Tnet) the averaged weights as a plain state_dict under "Tnet_ema" and {"decay", "updates"} under "ema" —
     "Tnet" stays the raw network, which a resumed run keeps training.  With ``schedule`` (a rcot_amd.schedule.Schedule) its counters under
-    "schedule": --resume continues at the stored iteration."""
+    "schedule": --resume continues at the stored iteration.  With ``best`` (a rcot_amd.valsuite.Best; --save_best) its record under
+    "best": {"key", "value", "epoch"}, and with ``is_best`` the same file once more as ..._best.pth."""
     path = "checkpoint/" + "model_" + str(opt.type) + "_" + "_" + str(opt.nEpochs) + "_" + str(opt.sigma) + ".pth"
     os.makedirs("checkpoint/", exist_ok=True)
     if not hasattr(Tnet, "decoder"):
@@ -727,8 +731,13 @@ def save_checkpoint(Tnet, Fnet, epoch, T_optimizer=None, F_optimizer=None, ema=N
         state["ema"] = {"decay": ema.decay, "updates": ema.updates}
     if schedule is not None:
         state["schedule"] = schedule.state_dict()
+    if best is not None:
+        state["best"] = best.state_dict()
     torch.save(state, path)
     print("Checkpoint saved to {}".format(path))
+    if best is not None and is_best:
+        torch.save(state, _valsuite.best_path(path))
+        print("Best {} {:.4f} (epoch {}): checkpoint also saved to {}".format(best.key, best.value, epoch, _valsuite.best_path(path)))
     return path
 
 
@@ -919,6 +928,11 @@ def main(argv=None):
     check_ema_flags(opt, stock_mprnet=opt.backbone == "mprnet" and not hip_mprnet)
     check_clip_flags(opt, stock_mprnet=opt.backbone == "mprnet" and not hip_mprnet)
     check_schedule_flags(opt, stock_mprnet=opt.backbone == "mprnet" and not hip_mprnet)
+    # --val_pad defaults to reflect once a --val_set is given: whether the flag itself was given shows in a namespace that holds no default
+    explicit_pad = opt.val_set is None or parser.parse_args(argv, namespace=argparse.Namespace(val_pad=None)).val_pad is not None
+    val_specs = _valsuite.check_flags(opt, stock_mprnet=opt.backbone == "mprnet" and not hip_mprnet, explicit_pad=explicit_pad)
+    if val_specs:                                                          # before any network is built: empty folders, the budget
+        _valsuite.check_budget(val_specs, _valsuite.list_sets(val_specs), opt.val_cache_gb)
     if opt.backbone == "mprnet" and not hip_mprnet:
         return main_mprnet()
     if "RANK" in os.environ and "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) > 1:
@@ -1014,6 +1028,12 @@ def main(argv=None):
     elif has_avg and rank == 0:
         print(f"=> '{opt.resume}' holds a weight average (\"Tnet_ema\"): ignored without --ema")
     sched_state = ck.get("schedule") if isinstance(ck, dict) else None
+    best = None
+    if opt.save_best is not None:
+        best = _valsuite.Best(opt.save_best, *_valsuite.parse_best_key(opt.save_best, val_specs))
+        note = best.load_state_dict(ck.get("best") if isinstance(ck, dict) else None)
+        if note and rank == 0:
+            print(f"=> '{opt.resume}' {note}")
     resumed = ck is not None
     ck = None
     if opt.synthetic:
@@ -1029,6 +1049,9 @@ def main(argv=None):
         loader = FolderLoader(opt, opt.batchSize // world, seed=seed, rank=rank, world=world, threads=opt.threads, cache=cache)
     import glob
     deg_list, tar_list = sorted(glob.glob(opt.degset + "*")), sorted(glob.glob(opt.tarset + "*"))   # :137-141
+    suite = None
+    if val_specs and rank == 0:                                            # rank 0 validates: the resident suite lives on its device
+        suite = _valsuite.ValSuite(default_backend(), val_specs, Tnet.size_multiple, opt.val_pad, opt.val_batch, opt.val_cache_gb)
     # the per-iteration schedule and / or the EMA warm-up: one block on the device per rank, every rank advances its own identical one
     sched = None
     if scheduled or opt.ema_warmup:
@@ -1066,8 +1089,16 @@ def main(argv=None):
             print(f"epoch {epoch}: {len(loader) * opt.batchSize / dt:.1f} patches/s")
             if getattr(loader, "cache", None) is not None:
                 print(loader.cache.report())
-            extra = ""
-            if avg is None or opt.val_weights == "raw":
+            extra, is_best = "", False
+            if suite is not None:                                          # --val_set: every set, one JSON object, the legacy line from its mean
+                print('----------validating-----------')
+                obj = _valsuite.validate(suite, Tnet, avg, opt.val_weights, epoch, f"ema{opt.ema:g}")
+                _valsuite.append_jsonl("./checksample/" + str(opt.type) + "/validation_suite.jsonl", obj)
+                p = obj["mean"].get("psnr_float", float("nan"))
+                if opt.val_weights == "both":
+                    extra = f", psnr_raw {obj['weights']['raw']['mean'].get('psnr_float', float('nan')):.4f}"
+                is_best = best is not None and best.update(obj, epoch)
+            elif avg is None or opt.val_weights == "raw":
                 p = evaluate(Tnet, deg_list, tar_list, pad=opt.val_pad)    # :149
             else:                                                          # --ema: on the averaged weights, the raw ones back afterwards
                 if opt.val_weights == "both":
@@ -1086,7 +1117,7 @@ def main(argv=None):
                 scio.savemat('PLOSSrain.mat', {'PLOSS': PLOSS})
             except ImportError:
                 pass
-            save_checkpoint(Tnet, Fnet, epoch, T_opt, F_opt, avg, sched)          # :165 (mprnet backbone: the state_dict form)
+            save_checkpoint(Tnet, Fnet, epoch, T_opt, F_opt, avg, sched, best, is_best)   # :165 (mprnet backbone: the state_dict form)
         if world > 1:
             torch.distributed.barrier()
     return Tnet, Fnet
