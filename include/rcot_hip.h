@@ -25,7 +25,7 @@ extern "C" {
 
 /* Bumped on EVERY signature change; returned by rcot_abi_version() (csrc/api.hip) and compared by the loader
  * (rcot_amd/lib.py ABI_VERSION, tests/test_abi.py) so that a stale prebuilt .so is refused, not mis-called. */
-#define RCOT_ABI_VERSION 41
+#define RCOT_ABI_VERSION 42
 
 /* Arithmetic of the MFMA products of the three GEMM-shaped entry points that take `prec` (rcot_gemm_kmajor,
  * rcot_conv1x1_wgrad, rcot_bmm_nt); operands and results are fp32 in memory either way.
@@ -95,6 +95,13 @@ int rcot_conv1x1_wgrad(const float* dY, long sdYb, const float* X, long sXb, flo
 int rcot_conv1x1_wgrad_slabs(const float* dY, long sdYb, const float* X, long sXb, int B, int Ci, int Co, int N,
                              const float* ln_mu, const float* ln_rs, const float* ln_w, const float* ln_b, float* ws,
                              size_t ws_bytes, int prec, int* S, int* ldws, void* stream);
+/* Sums slab sets and nothing else: for each of the n_sets (1..4) HOST rows { ws, S, M, N, ldws, dst, ldd } of slab_sets (the rows
+ * rcot_block_param_reduce takes, same checks): dst (M x N, leading dim ldd) += sum_s ws[s][M][ldws].  Per output the operands, the
+ * order of the additions and the final old + sum are those of rcot_block_param_reduce: handing a set to this launch instead gives
+ * the same bits.  For sets that are complete long before their block closes (the project_out / project_in weight gradients):
+ * summed on the stream that made them, the closing launch reads one set instead of three.  The launch is meant to run next to another
+ * stream's kernels: at most 64 workgroups walk the chunks of the sets, so that it does not take the memory system from them. */
+int rcot_slab_sets_reduce(const long long* slab_sets, int n_sets, void* stream);
 /* BOTH products of one incoming gradient dY of a 1x1 projection from ONE launch (bf16x3 arithmetic only):
  *   dX[b] (Ci x N) = W^T dY[b]         — rcot_conv1x1_dgrad on the packs WP / WPs of rcot_pack_weight (the K-major operand of the
  *                                        data gradient and its pre-split form), and

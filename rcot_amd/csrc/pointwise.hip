@@ -229,6 +229,136 @@ struct SlabSets {
     int n;
 };
 
+// The slab part of the launch above, also a launch of its own (slab_sets_reduce_kernel): workgroup ``cb`` of the sets' chunks, 1024 threads.
+__device__ __forceinline__ void slab_chunk_sum(const SlabSets& ss, int cb) {
+    __shared__ float part4[4][1024];
+    // ---- slab set d, ss.per[d] outputs per workgroup.  S > 8: thread = (one or four outputs, slab group q); S <= 8:
+    // outputs [4096 c, 4096 c + 4096), four outputs per thread with all their slabs in flight
+    int d = 0;
+    while (d + 1 < ss.n && cb >= ss.chunk0[d + 1]) ++d;
+    const int c = cb - ss.chunk0[d];
+    const long mn = (long)ss.M[d] * ss.N[d];
+    const long slab = (long)ss.M[d] * ss.ldws[d];
+    if (ss.S[d] <= 8) {
+        // four outputs per thread (1024 apart: every load of a wavefront is one contiguous 256-byte piece), all 4 x S slab reads and
+        // the four old values in flight before the first add; 32-bit index arithmetic (a weight gradient is far below 2^31
+        // elements; the 64-bit division of the one-output form was most of its instructions), loads from clamped indices
+        // instead of under branches.  Same sum, same order per output as before: bit-identical results (round 6: the launch
+        // that closes a 16 x 16 block 43 -> 2x us; it sits on the main stream behind a join in exact fp32)
+        const unsigned Nn = (unsigned)ss.N[d], mnu = (unsigned)mn, S = (unsigned)ss.S[d];
+        const unsigned ldw = (unsigned)ss.ldws[d];
+        const float* wsb = ss.ws[d];
+        float* dstb = ss.dst[d];
+        float v[4][8], old[4];
+        long doff[4];
+        bool ok[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const unsigned idx = (unsigned)c * 4096u + 1024u * j + threadIdx.x;
+            ok[j] = idx < mnu;
+            const unsigned ic = ok[j] ? idx : mnu - 1;
+            const unsigned m = ic / Nn, n = ic - m * Nn;
+            const float* w = wsb + (size_t)m * ldw + n;
+            doff[j] = (long)m * ss.ldd[d] + n;
+#pragma unroll
+            for (unsigned u = 0; u < 8; ++u) {
+                const unsigned uc = u < S ? u : S - 1;
+                v[j][u] = w[(long)uc * slab];
+            }
+            old[j] = dstb[doff[j]];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+#pragma unroll
+            for (unsigned u = 0; u < 8; ++u) v[j][u] = u < S ? v[j][u] : 0.f;
+            const float sum = ((v[j][0] + v[j][1]) + (v[j][2] + v[j][3])) + ((v[j][4] + v[j][5]) + (v[j][6] + v[j][7]));
+            if (ok[j]) dstb[doff[j]] = old[j] + sum;
+        }
+        return;
+    }
+    if (ss.per[d] == 256) {
+        // few outputs (the weight gradients of the 128 x 128 and 64 x 64 planes: 25 000 - 100 000 elements, up to 256 slabs each): one
+        // output per thread keeps 100 - 400 workgroups on the chip (four outputs per thread there: 33 -> 113 us, profiles/r06_block_reduce.txt)
+        const int o = threadIdx.x & 255, q = threadIdx.x >> 8;
+        const long idx = (long)c * 256 + o;
+        float* part = &part4[0][0];                                      // [4][256] at the start of the S > 8 scratch
+        float a = 0.f;
+        int m = 0, n = 0;
+        if (idx < mn) {
+            m = (int)(idx / ss.N[d]);
+            n = (int)(idx - (long)m * ss.N[d]);
+            const float* w = ss.ws[d] + (long)m * ss.ldws[d] + n;
+            float acc8[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) acc8[u] = 0.f;
+            int s = q;
+            for (; s + 28 < ss.S[d]; s += 32) {
+#pragma unroll
+                for (int u = 0; u < 8; ++u) acc8[u] += w[(long)(s + 4 * u) * slab];
+            }
+            for (; s < ss.S[d]; s += 4) acc8[0] += w[(long)s * slab];
+            a = ((acc8[0] + acc8[1]) + (acc8[2] + acc8[3])) + ((acc8[4] + acc8[5]) + (acc8[6] + acc8[7]));
+        }
+        part[q * 256 + o] = a;
+        __syncthreads();
+        if (q == 0 && idx < mn)
+            ss.dst[d][(long)m * ss.ldd[d] + n] += (part[o] + part[256 + o]) + (part[512 + o] + part[768 + o]);
+        return;
+    }
+    // S > 8: outputs [1024 c, 1024 c + 1024): thread (o, q) takes slab group q (slabs q, q + 4, ...) of the FOUR outputs o + 256 j —
+    // 32-bit index arithmetic, every load of a wavefront one contiguous 256-byte piece, up to 32 loads in flight per thread
+    // (round 6; one output per thread before: 6 500 workgroups for the three weight gradients of a 16 x 16 block).  Per output the
+    // sum and its order are unchanged (eight interleaved chains per group, then the four groups): bit-identical results.
+    const int o = threadIdx.x & 255, q = threadIdx.x >> 8;
+    const unsigned Nn = (unsigned)ss.N[d], mnu = (unsigned)mn, ldw = (unsigned)ss.ldws[d];
+    const int S = ss.S[d];
+    float a[4];
+    long doff[4];
+    bool ok[4];
+    const float* w[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const unsigned idx = (unsigned)c * 1024u + 256u * j + o;
+        ok[j] = idx < mnu;
+        const unsigned ic = ok[j] ? idx : mnu - 1;
+        const unsigned m = ic / Nn, n = ic - m * Nn;
+        w[j] = ss.ws[d] + (size_t)m * ldw + n;
+        doff[j] = (long)m * ss.ldd[d] + n;
+    }
+    float acc8[4][8];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc8[j][u] = 0.f;
+    int sl = q;
+    for (; sl + 28 < S; sl += 32) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int u = 0; u < 8; ++u) acc8[j][u] += w[j][(long)(sl + 4 * u) * slab];
+    }
+    for (; sl < S; sl += 4) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc8[j][0] += w[j][(long)sl * slab];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        a[j] = ((acc8[j][0] + acc8[j][1]) + (acc8[j][2] + acc8[j][3])) + ((acc8[j][4] + acc8[j][5]) + (acc8[j][6] + acc8[j][7]));
+#pragma unroll
+    for (int j = 0; j < 4; ++j) part4[q][256 * j + o] = a[j];
+    __syncthreads();
+    {   // thread t finishes output t of the chunk
+        const int t = threadIdx.x;
+        const unsigned idx = (unsigned)c * 1024u + t;
+        if (idx < mnu) {
+            const unsigned m = idx / Nn, n = idx - m * Nn;
+            ss.dst[d][(long)m * ss.ldd[d] + n] += (part4[0][t] + part4[1][t]) + (part4[2][t] + part4[3][t]);
+        }
+    }
+    (void)doff; (void)ok;
+    return;
+}
+
 __global__ __launch_bounds__(1024) void block_param_reduce_kernel(const float* __restrict__ part1, const float* __restrict__ part2,
                                                                   int rows, int C, float* __restrict__ gw1, float* __restrict__ gb1,
                                                                   float* __restrict__ gw2, float* __restrict__ gb2,
@@ -239,132 +369,7 @@ __global__ __launch_bounds__(1024) void block_param_reduce_kernel(const float* _
     const int nl = (2 * C + 31) / 32;
     const int blk = blockIdx.x;
     if (blk >= 2 * nl + nw) {
-        // ---- slab set d, ss.per[d] outputs per workgroup.  S > 8: thread = (one or four outputs, slab group q); S <= 8:
-        // outputs [4096 c, 4096 c + 4096), four outputs per thread with all their slabs in flight
-        const int cb = blk - 2 * nl - nw;
-        int d = 0;
-        while (d + 1 < ss.n && cb >= ss.chunk0[d + 1]) ++d;
-        const int c = cb - ss.chunk0[d];
-        const long mn = (long)ss.M[d] * ss.N[d];
-        const long slab = (long)ss.M[d] * ss.ldws[d];
-        if (ss.S[d] <= 8) {
-            // four outputs per thread (1024 apart: every load of a wavefront is one contiguous 256-byte piece), all 4 x S slab reads and
-            // the four old values in flight before the first add; 32-bit index arithmetic (a weight gradient is far below 2^31
-            // elements; the 64-bit division of the one-output form was most of its instructions), loads from clamped indices
-            // instead of under branches.  Same sum, same order per output as before: bit-identical results (round 6: the launch
-            // that closes a 16 x 16 block 43 -> 2x us; it sits on the main stream behind a join in exact fp32)
-            const unsigned Nn = (unsigned)ss.N[d], mnu = (unsigned)mn, S = (unsigned)ss.S[d];
-            const unsigned ldw = (unsigned)ss.ldws[d];
-            const float* wsb = ss.ws[d];
-            float* dstb = ss.dst[d];
-            float v[4][8], old[4];
-            long doff[4];
-            bool ok[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const unsigned idx = (unsigned)c * 4096u + 1024u * j + threadIdx.x;
-                ok[j] = idx < mnu;
-                const unsigned ic = ok[j] ? idx : mnu - 1;
-                const unsigned m = ic / Nn, n = ic - m * Nn;
-                const float* w = wsb + (size_t)m * ldw + n;
-                doff[j] = (long)m * ss.ldd[d] + n;
-#pragma unroll
-                for (unsigned u = 0; u < 8; ++u) {
-                    const unsigned uc = u < S ? u : S - 1;
-                    v[j][u] = w[(long)uc * slab];
-                }
-                old[j] = dstb[doff[j]];
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-#pragma unroll
-                for (unsigned u = 0; u < 8; ++u) v[j][u] = u < S ? v[j][u] : 0.f;
-                const float sum = ((v[j][0] + v[j][1]) + (v[j][2] + v[j][3])) + ((v[j][4] + v[j][5]) + (v[j][6] + v[j][7]));
-                if (ok[j]) dstb[doff[j]] = old[j] + sum;
-            }
-            return;
-        }
-        if (ss.per[d] == 256) {
-            // few outputs (the weight gradients of the 128 x 128 and 64 x 64 planes: 25 000 - 100 000 elements, up to 256 slabs each): one
-            // output per thread keeps 100 - 400 workgroups on the chip (four outputs per thread there: 33 -> 113 us, profiles/r06_block_reduce.txt)
-            const int o = threadIdx.x & 255, q = threadIdx.x >> 8;
-            const long idx = (long)c * 256 + o;
-            float* part = &red[0][0];                                        // [4][256] inside the 32 x 33 scratch
-            float a = 0.f;
-            int m = 0, n = 0;
-            if (idx < mn) {
-                m = (int)(idx / ss.N[d]);
-                n = (int)(idx - (long)m * ss.N[d]);
-                const float* w = ss.ws[d] + (long)m * ss.ldws[d] + n;
-                float acc8[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) acc8[u] = 0.f;
-                int s = q;
-                for (; s + 28 < ss.S[d]; s += 32) {
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) acc8[u] += w[(long)(s + 4 * u) * slab];
-                }
-                for (; s < ss.S[d]; s += 4) acc8[0] += w[(long)s * slab];
-                a = ((acc8[0] + acc8[1]) + (acc8[2] + acc8[3])) + ((acc8[4] + acc8[5]) + (acc8[6] + acc8[7]));
-            }
-            part[q * 256 + o] = a;
-            __syncthreads();
-            if (q == 0 && idx < mn)
-                ss.dst[d][(long)m * ss.ldd[d] + n] += (part[o] + part[256 + o]) + (part[512 + o] + part[768 + o]);
-            return;
-        }
-        // S > 8: outputs [1024 c, 1024 c + 1024): thread (o, q) takes slab group q (slabs q, q + 4, ...) of the FOUR outputs o + 256 j —
-        // 32-bit index arithmetic, every load of a wavefront one contiguous 256-byte piece, up to 32 loads in flight per thread
-        // (round 6; one output per thread before: 6 500 workgroups for the three weight gradients of a 16 x 16 block).  Per output the
-        // sum and its order are unchanged (eight interleaved chains per group, then the four groups): bit-identical results.
-        const int o = threadIdx.x & 255, q = threadIdx.x >> 8;
-        const unsigned Nn = (unsigned)ss.N[d], mnu = (unsigned)mn, ldw = (unsigned)ss.ldws[d];
-        const int S = ss.S[d];
-        float a[4];
-        long doff[4];
-        bool ok[4];
-        const float* w[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const unsigned idx = (unsigned)c * 1024u + 256u * j + o;
-            ok[j] = idx < mnu;
-            const unsigned ic = ok[j] ? idx : mnu - 1;
-            const unsigned m = ic / Nn, n = ic - m * Nn;
-            w[j] = ss.ws[d] + (size_t)m * ldw + n;
-            doff[j] = (long)m * ss.ldd[d] + n;
-        }
-        float acc8[4][8];
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int u = 0; u < 8; ++u) acc8[j][u] = 0.f;
-        int sl = q;
-        for (; sl + 28 < S; sl += 32) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int u = 0; u < 8; ++u) acc8[j][u] += w[j][(long)(sl + 4 * u) * slab];
-        }
-        for (; sl < S; sl += 4) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc8[j][0] += w[j][(long)sl * slab];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            a[j] = ((acc8[j][0] + acc8[j][1]) + (acc8[j][2] + acc8[j][3])) + ((acc8[j][4] + acc8[j][5]) + (acc8[j][6] + acc8[j][7]));
-        __shared__ float part4[4][1024];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) part4[q][256 * j + o] = a[j];
-        __syncthreads();
-        {   // thread t finishes output t of the chunk
-            const int t = threadIdx.x;
-            const unsigned idx = (unsigned)c * 1024u + t;
-            if (idx < mnu) {
-                const unsigned m = idx / Nn, n = idx - m * Nn;
-                ss.dst[d][(long)m * ss.ldd[d] + n] += (part4[0][t] + part4[1][t]) + (part4[2][t] + part4[3][t]);
-            }
-        }
-        (void)doff; (void)ok;
+        slab_chunk_sum(ss, blk - 2 * nl - nw);
         return;
     }
     if (blk < 2 * nl) {
@@ -417,6 +422,22 @@ __global__ __launch_bounds__(1024) void block_param_reduce_kernel(const float* _
         float s = 0.f;
         for (int b = 0; b < B; ++b) s += dtemp_part[(long)b * heads + threadIdx.x];
         gtemp[threadIdx.x] += s;
+    }
+}
+
+// dst += sum_s slab[s] for up to four slab sets and nothing else (rcot_slab_sets_reduce): the slab workgroups of the launch above in a
+// launch of their own, so that sets which are complete long before the block closes can be summed where a stream is idle.  That launch
+// runs NEXT TO the other stream's kernels: on a grid of all its chunks (100 - 1150 workgroups) it takes the memory system for 35 - 70 us
+// and the latency-bound kernels beside it last up to twice as long (the 64-workgroup dM product 39 -> 67 us), which gave back 0.56 of
+// the 1.33 ms per step the closing launch lost.  So at most SLAB_SETS_WGS workgroups walk the chunks: the sum has 140 - 300 us of idle
+// stream to finish in.  ms per step, exact fp32, B = 8, 128 x 128, four alternating rounds: all chunks 73.29, 96 workgroups 72.89,
+// 64: 72.47, 48: 72.67, 32: 74.25, 16: 79.8 (too few: presumably the sum is then in the way of the qkv weight gradient) — profiles/early_slab_sums.txt
+constexpr int SLAB_SETS_WGS = 64;
+__global__ __launch_bounds__(1024) void slab_sets_reduce_kernel(SlabSets ss) {
+    const int total = ss.chunk0[ss.n];
+    for (int cb = blockIdx.x; cb < total; cb += gridDim.x) {
+        slab_chunk_sum(ss, cb);
+        __syncthreads();                  // the next chunk re-uses the LDS scratch (the form is uniform over a workgroup: every thread arrives)
     }
 }
 
@@ -598,6 +619,27 @@ int rcot_ln_bwd_rows(int B, int C, int N) {
     return ln_bwd_grid(B, N, &wide) * B;
 }
 
+// HOST rows { ws, S, M, N, ldws, dst, ldd } -> the kernels' SlabSets; returns the number of chunks (workgroups) of all sets, -1 for a
+// row that cannot be.  The one place that decides how many outputs a workgroup of a set takes.
+static int slab_sets_fill(SlabSets& ss, const long long* slab_sets, int n_sets) {
+    ss.n = n_sets;
+    int chunks = 0;
+    for (int d = 0; d < n_sets; ++d) {
+        const long long* r = slab_sets + 7 * d;
+        ss.ws[d] = reinterpret_cast<const float*>(r[0]);
+        ss.S[d] = (int)r[1]; ss.M[d] = (int)r[2]; ss.N[d] = (int)r[3]; ss.ldws[d] = (int)r[4];
+        ss.dst[d] = reinterpret_cast<float*>(r[5]);
+        ss.ldd[d] = r[6];
+        if (!ss.ws[d] || !ss.dst[d] || ss.S[d] <= 0 || ss.M[d] <= 0 || ss.N[d] <= 0 || ss.ldws[d] < ss.N[d]) return -1;
+        ss.chunk0[d] = chunks;
+        const long mn_ = (long)ss.M[d] * ss.N[d];
+        ss.per[d] = ss.S[d] <= 8 ? 4096 : (mn_ >= 256 * 1024 ? 1024 : 256);
+        chunks += cdiv(mn_, ss.per[d]);
+    }
+    ss.chunk0[n_sets] = chunks;
+    return chunks;
+}
+
 int rcot_block_param_reduce(const float* part1, const float* part2, int rows, int C, float* gw1, float* gb1, float* gw2,
                             float* gb2, const float* dWo_part, float* gWo, const float* dtemp_part, float* gtemp, int B,
                             int heads, const long long* slab_sets, int n_sets, void* stream) {
@@ -607,23 +649,20 @@ int rcot_block_param_reduce(const float* part1, const float* part2, int rows, in
     const int nl = cdiv(2 * C, 32);
     const int nw = cdiv((long)C * C, 1024);
     SlabSets ss{};
-    ss.n = n_sets;
-    int chunks = 0;
-    for (int d = 0; d < n_sets; ++d) {                                  // HOST rows { ws, S, M, N, ldws, dst, ldd }
-        const long long* r = slab_sets + 7 * d;
-        ss.ws[d] = reinterpret_cast<const float*>(r[0]);
-        ss.S[d] = (int)r[1]; ss.M[d] = (int)r[2]; ss.N[d] = (int)r[3]; ss.ldws[d] = (int)r[4];
-        ss.dst[d] = reinterpret_cast<float*>(r[5]);
-        ss.ldd[d] = r[6];
-        if (!ss.ws[d] || !ss.dst[d] || ss.S[d] <= 0 || ss.M[d] <= 0 || ss.N[d] <= 0 || ss.ldws[d] < ss.N[d]) return RCOT_EINVAL;
-        ss.chunk0[d] = chunks;
-        const long mn_ = (long)ss.M[d] * ss.N[d];
-        ss.per[d] = ss.S[d] <= 8 ? 4096 : (mn_ >= 256 * 1024 ? 1024 : 256);
-        chunks += cdiv(mn_, ss.per[d]);
-    }
-    ss.chunk0[n_sets] = chunks;
+    const int chunks = slab_sets_fill(ss, slab_sets, n_sets);
+    if (chunks < 0) return RCOT_EINVAL;
     RCOT_LAUNCH(block_param_reduce_kernel, dim3(2 * nl + nw + chunks), dim3(1024), 0, (hipStream_t)stream, part1, part2, rows,
                        C, gw1, gb1, gw2, gb2, dWo_part, gWo, dtemp_part, gtemp, B, heads, nw, ss);
+    RCOT_LAUNCH_CHECK();
+    return RCOT_OK;
+}
+
+int rcot_slab_sets_reduce(const long long* slab_sets, int n_sets, void* stream) {
+    if (!slab_sets || n_sets < 1 || n_sets > 4) return RCOT_EINVAL;
+    SlabSets ss{};
+    const int chunks = slab_sets_fill(ss, slab_sets, n_sets);
+    if (chunks < 0) return RCOT_EINVAL;
+    RCOT_LAUNCH(slab_sets_reduce_kernel, dim3(chunks < SLAB_SETS_WGS ? chunks : SLAB_SETS_WGS), dim3(1024), 0, (hipStream_t)stream, ss);
     RCOT_LAUNCH_CHECK();
     return RCOT_OK;
 }

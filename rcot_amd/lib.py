@@ -9,7 +9,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 41    # == RCOT_ABI_VERSION in include/rcot_hip.h (checked by tests/test_abi.py and at load time)
+ABI_VERSION = 42    # == RCOT_ABI_VERSION in include/rcot_hip.h (checked by tests/test_abi.py and at load time)
 PREC_FP32, PREC_BF16X3, PREC_BF16X6, PREC_BF16X1 = 0, 1, 2, 3     # RCOT_PREC_* of include/rcot_hip.h
 # the control block of a guarded optimizer (include/rcot_hip.h): word indices into a float64 tensor of CB_WORDS (the I words through .view(int64))
 SUMSQ_MAX_PARTS, CB_WORDS = 4096, 16
@@ -84,6 +84,7 @@ SIGNATURES = {
     "rcot_ln_bwd": [_f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _f, _l, _f],
     "rcot_ln_bwd_rows": [_i, _i, _i],
     "rcot_block_param_reduce": [_f, _f, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _f, _i, _f],   # slab_sets: HOST array
+    "rcot_slab_sets_reduce": [_f, _i, _f],                                                            # slab_sets: HOST array
     "rcot_dwconv3x3": [_f, _f, _f, _i, _i, _i, _i, _i, _f],
     "rcot_gdfn_gate_fwd": [_f, _f, _f, _i, _i, _i, _i, _f],
     "rcot_gdfn_gate_bwd": [_f, _f, _f, _f, _f, _i, _i, _i, _i, _f],

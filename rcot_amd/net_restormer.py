@@ -153,22 +153,28 @@ class TransformerBlockOp:
             be.conv1x1_wgrad(dY, X, gW, ln=ln, beta=1.0)
         return d
 
-    def _dgrad_wgrad(self, slabs, W, dY, dX, X, gW, ln, packed, part):
+    def _dgrad_wgrad(self, slabs, W, dY, dX, X, gW, ln, packed, part, then=None):
         """The two products of one incoming gradient of a 1x1 projection: dX = W^T dY and gW += dY LN?(X)^T (as slabs in third
         ``part`` of the slab arena where the backend can).  ONE launch where the backend has the paired kernel (workgroups of both
-        products in one grid); else the weight gradient goes to the side stream next to the data-gradient chain."""
+        products in one grid); else the weight gradient goes to the side stream next to the data-gradient chain, ``then()`` right
+        behind it in the same side_run (no hand-over of its own), and the result is True."""
         be = self.be
         pair = getattr(be, "conv1x1_dgrad_wgrad_slabs", None)
         d = pair(W, dY, dX, X, gW, ln=ln, packed=packed, region=(part, 3)) if pair is not None else None
         if d is not None:
             slabs.append(d)
-            return
+            return False
         hold = (dY, X) + ((ln[0], ln[1]) if ln is not None else ())
         # (the weight gradient starts WITH its data gradient: started behind it — next to the bandwidth- / latency-bound kernels that follow
         # instead of next to another MFMA-bound product — it closes the block later: 77.2 -> 81.3 ms per iteration in exact fp32, 74.0 -> 76.5
         # in bf16x6, profiles/r05_ab_wgrad_after.txt)
-        be.side_run(lambda: slabs.append(self._wgrad(dY, X, gW, ln, part)), *hold)
+        def leaf():
+            slabs.append(self._wgrad(dY, X, gW, ln, part))
+            if then is not None:
+                then()
+        be.side_run(leaf, *hold)
         be.conv1x1_dgrad(W, dY, dX, packed=packed)
+        return True
 
     def _woT_heads(self, B):
         """W_o^T (from the pack) as [B (broadcast), heads, c, C]: rows h*c+i of W_o^T for every head."""
@@ -263,12 +269,23 @@ class TransformerBlockOp:
         # ---- GDFN
         slabs = []       # weight gradients left as split-K slabs on the side stream; block_param_reduce() adds them up
         dg = be.empty(B, hid, H, W)
-        self._dgrad_wgrad(slabs, self.Wout, dout, dg, gg, self.gWout, None, self.pk_out, 0)
+        on_side = self._dgrad_wgrad(slabs, self.Wout, dout, dg, gg, self.gWout, None, self.pk_out, 0)
+        # early slab sums (HipBackend.early_slab_sums): the project_out / project_in slab sets are complete long before the block closes,
+        # and the side stream is idle from the second of them to the qkv weight gradient.  Summed there, behind their writers on the
+        # same stream, they leave the closing launch (alone on the main stream in exact fp32) the qkv set only; the next writers of
+        # arena parts 0 and 1 are behind that launch's join.  Same operands and order per output as in the closing launch: same bits.
+        early = getattr(be, "slab_sets_reduce", None) if getattr(be, "early_slab_sums", False) and on_side else None
+
+        def early_sum():
+            if len(slabs) == 2 and slabs[0] is not None and slabs[1] is not None:
+                early(slabs)
+                del slabs[:]
         dp = be.empty(B, 2 * hid, H, W)
         be.gdfn_bwd(pp, self.Wdw2, dg, dp, self.gWdw2)    # gate backward, rotated depthwise conv and its weight gradient: one pass
         del dg
         gln = be.empty(B, C, H, W)
-        self._dgrad_wgrad(slabs, self.Win, dp, gln, y, self.gWin, (mu2, rs2, self.w2, self.b2), self.pk_in, 1)
+        self._dgrad_wgrad(slabs, self.Win, dp, gln, y, self.gWin, (mu2, rs2, self.w2, self.b2), self.pk_in, 1,
+                          then=early_sum if early is not None else None)
         del dp
         dy = be.empty(B, C, H, W)
         be.ln_bwd(gln, y, mu2, rs2, self.w2, dout, dy, None, None, slot=0)     # norm2: dw/db partials deferred (slot 0)

@@ -263,6 +263,11 @@ class HipBackend:
         # bf16x6 only — fp32 77.06 -> 78.04 ms per iteration, bf16x6 73.03 -> 72.48, bf16x3 70.13 -> 70.71
         # (profiles/r06_ab_sched_nofence.txt; the earlier rounds' runs are in NOTES.md)
         self._defer_close_env = os.environ.get("RCOT_DEFER_CLOSE")
+        # Early slab sums: the project_out / project_in weight-gradient slabs of a block are added up on the side stream right behind
+        # the second of them (slab_sets_reduce), where that stream is idle, so that the closing launch reads the qkv set only.
+        # Per iteration, off -> on, five alternating pairs each: fp32 73.31 -> 72.25 ms, bf16x6 70.89 -> 70.14, bf16x3 68.66 -> 68.58
+        # (inside its 0.35 ms spread: off; its small planes make their slabs on the main stream anyway) — profiles/early_slab_sums.txt
+        self._early_slabs_env = os.environ.get("RCOT_EARLY_SLABS")
 
     # ------------------------------------------------------------------ leaf-kernel overlap
     @property
@@ -271,6 +276,13 @@ class HipBackend:
         if self._defer_close_env is not None:
             return self._defer_close_env != "0"
         return self.prec == _lib.PREC_BF16X6
+
+    @property
+    def early_slab_sums(self):
+        """the first two weight-gradient slab sets of a block are summed early on the side stream (policy above); RCOT_EARLY_SLABS=0/1 overrides"""
+        if self._early_slabs_env is not None:
+            return self._early_slabs_env != "0"
+        return self.prec in (_lib.PREC_FP32, _lib.PREC_BF16X6)
 
     def side_run(self, fn, *hold):
         """Run ``fn`` (kernel launches that only READ ``hold`` tensors and WRITE parameter gradients) on the side
@@ -1057,6 +1069,15 @@ class HipBackend:
                 self._host(lambda: torch.cuda.current_stream().wait_event(ev))
             self._gen_event[gen] = None
             self._held_gen[gen].clear()
+
+    def slab_sets_reduce(self, slabs):
+        """every descriptor of ``slabs`` (conv1x1_wgrad_slabs, at most 4): its weight gradient += the sum of its slabs, bit for bit what
+        block_param_reduce() would add, on the current stream (rcot_slab_sets_reduce); nothing is launched for an empty list."""
+        slabs = [d for d in slabs if d is not None]
+        if not slabs:
+            return
+        rows = (ctypes_ll * (7 * len(slabs)))(*[v for d in slabs for v in d])
+        _lib.check(self.L.rcot_slab_sets_reduce(rows, len(slabs), self._st()), "rcot_slab_sets_reduce")
 
     def block_param_reduce(self, C, gw1, gb1, gw2, gb2, dWo_part, gWo, dtemp_part, gtemp, slabs=(), close_block=False):
         """LN partials of scratch slot 0 -> (gw1, gb1), slot 1 -> (gw2, gb2); gWo += dWo_part.sum(0); gtemp += dtemp_part.sum(0);

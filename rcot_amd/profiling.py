@@ -14,7 +14,7 @@ GEMM_OPS = ("gemm_kmajor", "gemm_kmajor_stats", "gemm_kmajor_multi", "conv1x1_fw
             "bmm_nt_slabs", "linear_fwd", "linear_dgrad",
             "linear_wgrad", "conv2d_fwd", "conv2d_dgrad", "conv2d_wgrad")
 OTHER_OPS = ("ln_stats", "ln_bwd", "dwconv3x3", "gdfn_gate_fwd", "gdfn_gate_bwd", "gdfn_bwd", "dwconv3x3_wgrad", "dwconv3x3_bwd", "row_sumsq",
-             "attn_softmax", "attn_bwd_small", "batch_reduce", "block_param_reduce", "lrelu_bwd", "bias_grad", "axpby", "fill", "lerp", "gp_penalty",
+             "attn_softmax", "attn_bwd_small", "batch_reduce", "block_param_reduce", "slab_sets_reduce", "lrelu_bwd", "bias_grad", "axpby", "fill", "lerp", "gp_penalty",
              "pixel_shuffle", "pack_weight", "ot_reduce", "ot_spectrum", "ot_grad", "rmsprop_step", "adam_step",
              "grad_sumsq", "grad_decide", "rmsprop_step_guarded", "adam_step_guarded")
 
@@ -113,12 +113,16 @@ class OpTimer:
             nbytes = 4.0 * (sum(_numel(t) for t in a) + sum(_numel(t) for t in kw.values()))
             if name == "gemm_kmajor_multi":
                 nbytes = 4.0 * sum(_numel(t) for it in a[0] for t in it)
+            if name == "slab_sets_reduce":       # descriptors (ws, S, M, N, ldws, dst, ldd), not tensors: the slabs once, dst read and written
+                nbytes = 4.0 * sum(d[1] * d[2] * d[3] + 2 * d[2] * d[3] for d in a[0] if d is not None)
             ln = kw.get("ln")
             if ln is not None:
                 nbytes += 4.0 * sum(_numel(t) for t in ln)
             key = name + str(tuple(tuple(t.shape) for t in (a[:4] if name != "gemm_kmajor_multi" else [it[2] for it in a[0]]) if isinstance(t, torch.Tensor)))
             if ln is not None:
                 key += "+ln"
+            if name == "slab_sets_reduce":
+                key += str(tuple(d[1:4] for d in a[0] if d is not None))
             self.records.append((name, s, e, _flops(name, a, kw) if gemm else 0.0, nbytes, key, sym))
             if key not in self._calls:
                 self._calls[key] = (fn, a, kw)
