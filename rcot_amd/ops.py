@@ -197,6 +197,9 @@ _TWO_TERM = (_lib.PREC_BF16X3, _lib.PREC_BF16X1)      # the arithmetics that run
 #: reference's arithmetic.  bf16x6 gives results as close to fp64 (tests/test_x3_gpu.py::test_x6_is_as_accurate_as_the_fp32_kernel;
 #: every parity test holds the fp32 bars in it) 2 % faster end to end, bf16x3 results within the north_star tolerances 15 % faster.
 DEFAULT_PREC = "fp32"
+#: floats in each of HipBackend._ln_scratch's buffers: the deferred partial rows of one LayerNorm backward, rcot_ln_bwd_rows(B, C, N)
+#: rows of 2 C floats (<= 1024 rows x 2 * 512 columns for every B <= 1024; tests/test_ln_forms_cpu.py holds the trainer's shapes to it)
+LN_SCRATCH_FLOATS = 1024 * 1024
 
 
 def default_backend():
@@ -254,7 +257,7 @@ class HipBackend:
         # deferred LayerNorm parameter-gradient partials of one block (<= 1024 rows x 2*512 columns each), in TWO generations:
         # the launch that closes a block (block_param_reduce) runs on the side stream behind that block's weight-gradient
         # kernels while the main stream is already in the next block, which therefore writes the other generation
-        self._ln_scratch = [[torch.empty(1024 * 1024, dtype=torch.float32, device=self.device) for _ in range(2)] for _ in range(2)]
+        self._ln_scratch = [[torch.empty(LN_SCRATCH_FLOATS, dtype=torch.float32, device=self.device) for _ in range(2)] for _ in range(2)]
         self._ln_rows = 0
         self._gen = 0
         self._gen_event = [None, None]          # side-stream event after the reduce that read generation g
