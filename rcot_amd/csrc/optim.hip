@@ -8,45 +8,104 @@ namespace {
 
 using rcot::al16;
 
-// The per-element updates, shared by the plain and the guarded kernels below (one expression each, so that a guarded step with
-// scale 1 is the same arithmetic as the plain one).  They read gv, gscale and the hyper-parameters of the enclosing kernel.
-#define RCOT_RMS(c)                                        \
-    {                                                      \
-        const float gg = gv.c * gscale;                    \
-        sv.c = alpha * sv.c + oma * gg * gg;     \
-        pv.c -= lr * gg / (sqrtf(sv.c) + eps);             \
-    }
-#define RCOT_ADAM(c)                                                     \
-    {                                                                    \
-        const float gg = gv.c * gscale;                                  \
-        mv.c = b1 * mv.c + omb1 * gg;                              \
-        vv.c = b2 * vv.c + omb2 * gg * gg;                         \
-        pv.c -= step_size * mv.c / (sqrtf(vv.c) * rsqrt_bc2 + eps);     \
-    }
+// ---- the optimizer steps: ONE kernel, a rule (what happens to one element) x a source (where the launch's scalars come from) ----
+// What may change from one iteration to the next.  lr: RMSprop's rate; for Adam the step size lr / (1 - b1^t).  rsqrt_bc2: 1 / sqrt(1 - b2^t).
+// gscale: the factor on the gradient (a loss scale, or the clipping decision).  nlrwd: AdamW's -(float)(lr wd), the product formed in double.
+struct StepScalars {
+    float lr, rsqrt_bc2, gscale, nlrwd;
+};
 
-__global__ __launch_bounds__(256) void rmsprop_kernel(float4* __restrict__ p, const float4* __restrict__ g,
-                                                      float4* __restrict__ sq, long n4, float lr, float alpha, float oma,
-                                                      float eps, float gscale) {
+// The rules: hyper-parameters that never change, the number of state buffers, and what happens to one element: decay() (AdamW's alone
+// does something), then the update — one expression each, so that a guarded step with scale 1 is the same arithmetic as the plain one.
+struct RmsProp {
+    static constexpr int kStates = 1;
+    static constexpr bool kAdam = false, kDecay = false;
+    float alpha, oma, eps;
+    __device__ __forceinline__ void decay(float&, const StepScalars&) const {}
+    __device__ __forceinline__ void operator()(float& p, float g, float& s, float&, const StepScalars& k) const {
+        const float gg = g * k.gscale;
+        s = alpha * s + oma * gg * gg;
+        p -= k.lr * gg / (sqrtf(s) + eps);
+    }
+};
+
+// AdamW (torch.optim.AdamW): decoupled weight decay p <- p - (lr wd) p before Adam's update, as one fused multiply-add in the increment
+// form.  The factor form (float)(1 - lr wd) would round 1 - 3e-8 (lr 3e-4, wd 1e-4) to 1 - 2^-24: twice the decay asked for.  Adam's
+// bytes, plus one FMA per element.
+template <bool Decay>
+struct AdamRule {
+    static constexpr int kStates = 2;
+    static constexpr bool kAdam = true, kDecay = Decay;
+    float b1, b2, omb1, omb2, eps;
+    __device__ __forceinline__ void decay(float& p, const StepScalars& k) const {
+        if constexpr (Decay) p = __builtin_fmaf(k.nlrwd, p, p);
+    }
+    __device__ __forceinline__ void operator()(float& p, float g, float& m, float& v, const StepScalars& k) const {
+        const float gg = g * k.gscale;
+        m = b1 * m + omb1 * gg;
+        v = b2 * v + omb2 * gg * gg;
+        p -= k.lr * m / (sqrtf(v) * k.rsqrt_bc2 + eps);
+    }
+};
+using Adam = AdamRule<false>;
+using AdamW = AdamRule<true>;
+
+// The sources.  read() fills what the rule uses and says whether the launch does anything.
+struct ByValue {
+    StepScalars k;
+    template <class Rule> __device__ __forceinline__ bool read(StepScalars& o) const {
+        o = k;
+        return true;
+    }
+};
+
+// The control block (uniform loads of words that the decision launch, the host or the schedule's advance launch wrote).  A skipped step
+// says no before anything is loaded: p and the state stay bit for bit what they were.  counter: which of the block's two Adam step
+// counts this range follows; a count of 0 (no taken decision has advanced it) has no bias correction, and the launch does nothing.
+// lr wd is formed here, in double, from the block's learning rate.
+struct FromCtrl {
+    const double* ctrl;
+    int counter;
+    double wd;
+    template <class Rule> __device__ __forceinline__ bool read(StepScalars& o) const {
+        const long long* ci = reinterpret_cast<const long long*>(ctrl);
+        if (ci[RCOT_CB_SKIP]) return false;
+        if constexpr (Rule::kAdam) {
+            if (ci[RCOT_CB_T + counter] <= 0) return false;
+            o.lr = (float)(ctrl[RCOT_CB_LR] / ctrl[RCOT_CB_BC1 + counter]);
+            o.rsqrt_bc2 = (float)(1.0 / sqrt(ctrl[RCOT_CB_BC2 + counter]));
+        } else {
+            o.lr = (float)ctrl[RCOT_CB_LR];
+        }
+        o.gscale = (float)ctrl[RCOT_CB_SCALE];
+        if constexpr (Rule::kDecay) o.nlrwd = -(float)(ctrl[RCOT_CB_LR] * wd);
+        return true;
+    }
+};
+
+// s1: the second state buffer of a rule that has one (never touched otherwise)
+template <class Rule, class Src>
+__global__ __launch_bounds__(256) void step_kernel(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ s0,
+                                                   float4* __restrict__ s1, long n4, Rule rule, Src src) {
+    StepScalars k{};
+    if (!src.template read<Rule>(k)) return;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-        float4 pv = p[i], gv = g[i], sv = sq[i];
-        RCOT_RMS(x) RCOT_RMS(y) RCOT_RMS(z) RCOT_RMS(w)
+        float4 pv = p[i], gv = g[i], av = s0[i], bv{};
+        if constexpr (Rule::kStates == 2) bv = s1[i];
+        rule.decay(pv.x, k);                     // (all four before the first update: the loop's schedule follows the statement order)
+        rule.decay(pv.y, k);
+        rule.decay(pv.z, k);
+        rule.decay(pv.w, k);
+        rule(pv.x, gv.x, av.x, bv.x, k);
+        rule(pv.y, gv.y, av.y, bv.y, k);
+        rule(pv.z, gv.z, av.z, bv.z, k);
+        rule(pv.w, gv.w, av.w, bv.w, k);
         p[i] = pv;
-        sq[i] = sv;
+        s0[i] = av;
+        if constexpr (Rule::kStates == 2) s1[i] = bv;
     }
 }
 
-__global__ __launch_bounds__(256) void adam_kernel(float4* __restrict__ p, const float4* __restrict__ g,
-                                                   float4* __restrict__ m, float4* __restrict__ v, long n4, float lr,
-                                                   float b1, float b2, float omb1, float omb2, float eps, float step_size, float rsqrt_bc2,
-                                                   float gscale) {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-        float4 pv = p[i], gv = g[i], mv = m[i], vv = v[i];
-        RCOT_ADAM(x) RCOT_ADAM(y) RCOT_ADAM(z) RCOT_ADAM(w)
-        p[i] = pv;
-        m[i] = mv;
-        v[i] = vv;
-    }
-}
 // Weight average: ema += omd * (p - ema), one fused multiply-add per element (3 streams of 4 B per element).  The increment form keeps
 // p - ema exact (or nearly so) where the two are close, which is what an fp32 average at decay 0.999 rests on.
 // vec: n4 float4 elements grid-stride, then the n - 4 n4 <= 3 tail elements by the first lanes of workgroup 0; else n scalars.
@@ -172,80 +231,6 @@ __global__ __launch_bounds__(256) void decide_kernel(const double* __restrict__ 
     }
 }
 
-// The plain kernels with the learning rate, the scale and the skip flag read from the control block (uniform loads of words that the
-// decision launch wrote).  A skipped step returns before it loads anything: p and the state stay bit for bit what they were.
-__global__ __launch_bounds__(256) void rmsprop_guarded_kernel(float4* __restrict__ p, const float4* __restrict__ g,
-                                                              float4* __restrict__ sq, long n4, float alpha, float oma, float eps,
-                                                              const double* __restrict__ ctrl) {
-    if (reinterpret_cast<const long long*>(ctrl)[RCOT_CB_SKIP]) return;
-    const float lr = (float)ctrl[RCOT_CB_LR], gscale = (float)ctrl[RCOT_CB_SCALE];
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-        float4 pv = p[i], gv = g[i], sv = sq[i];
-        RCOT_RMS(x) RCOT_RMS(y) RCOT_RMS(z) RCOT_RMS(w)
-        p[i] = pv;
-        sq[i] = sv;
-    }
-}
-
-// counter: which of the block's two Adam step counts this range follows.  A count of 0 (no taken decision has advanced it) has no bias
-// correction: the launch does nothing.
-__global__ __launch_bounds__(256) void adam_guarded_kernel(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ m,
-                                                           float4* __restrict__ v, long n4, float b1, float b2, float omb1, float omb2,
-                                                           float eps, const double* __restrict__ ctrl, int counter) {
-    const long long* ci = reinterpret_cast<const long long*>(ctrl);
-    if (ci[RCOT_CB_SKIP] || ci[RCOT_CB_T + counter] <= 0) return;
-    const float step_size = (float)(ctrl[RCOT_CB_LR] / ctrl[RCOT_CB_BC1 + counter]);
-    const float rsqrt_bc2 = (float)(1.0 / sqrt(ctrl[RCOT_CB_BC2 + counter]));
-    const float gscale = (float)ctrl[RCOT_CB_SCALE];
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-        float4 pv = p[i], gv = g[i], mv = m[i], vv = v[i];
-        RCOT_ADAM(x) RCOT_ADAM(y) RCOT_ADAM(z) RCOT_ADAM(w)
-        p[i] = pv;
-        m[i] = mv;
-        v[i] = vv;
-    }
-}
-
-// AdamW (torch.optim.AdamW): decoupled weight decay p <- p - (lr wd) p before Adam's update, as one fused multiply-add in the increment
-// form — nlrwd = -(float)(lr wd), the product formed in double.  The factor form (float)(1 - lr wd) would round 1 - 3e-8 (lr 3e-4,
-// wd 1e-4) to 1 - 2^-24: twice the decay asked for.  Adam's bytes, plus one FMA per element; RCOT_ADAM is the expression of adam_kernel.
-#define RCOT_WD(c) pv.c = __builtin_fmaf(nlrwd, pv.c, pv.c);
-__global__ __launch_bounds__(256) void adamw_kernel(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ m,
-                                                    float4* __restrict__ v, long n4, float b1, float b2, float omb1, float omb2, float eps,
-                                                    float step_size, float rsqrt_bc2, float gscale, float nlrwd) {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-        float4 pv = p[i], gv = g[i], mv = m[i], vv = v[i];
-        RCOT_WD(x) RCOT_WD(y) RCOT_WD(z) RCOT_WD(w)
-        RCOT_ADAM(x) RCOT_ADAM(y) RCOT_ADAM(z) RCOT_ADAM(w)
-        p[i] = pv;
-        m[i] = mv;
-        v[i] = vv;
-    }
-}
-
-// adam_guarded_kernel with the decay: lr wd is formed here, in double, from the block's learning rate.
-__global__ __launch_bounds__(256) void adamw_guarded_kernel(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ m,
-                                                            float4* __restrict__ v, long n4, float b1, float b2, float omb1, float omb2,
-                                                            float eps, const double* __restrict__ ctrl, int counter, double wd) {
-    const long long* ci = reinterpret_cast<const long long*>(ctrl);
-    if (ci[RCOT_CB_SKIP] || ci[RCOT_CB_T + counter] <= 0) return;
-    const float step_size = (float)(ctrl[RCOT_CB_LR] / ctrl[RCOT_CB_BC1 + counter]);
-    const float rsqrt_bc2 = (float)(1.0 / sqrt(ctrl[RCOT_CB_BC2 + counter]));
-    const float gscale = (float)ctrl[RCOT_CB_SCALE];
-    const float nlrwd = -(float)(ctrl[RCOT_CB_LR] * wd);
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-        float4 pv = p[i], gv = g[i], mv = m[i], vv = v[i];
-        RCOT_WD(x) RCOT_WD(y) RCOT_WD(z) RCOT_WD(w)
-        RCOT_ADAM(x) RCOT_ADAM(y) RCOT_ADAM(z) RCOT_ADAM(w)
-        p[i] = pv;
-        m[i] = mv;
-        v[i] = vv;
-    }
-}
-#undef RCOT_WD
-#undef RCOT_RMS
-#undef RCOT_ADAM
-
 // ---- per-iteration schedules held on the device (schedule block: include/rcot_hip.h, RCOT_SB_*) ----
 // ONE workgroup, one lane of it: the iteration's rate from the table into the block and into up to two destination words (the
 // RCOT_CB_LR words of the two optimizers), the counter, and the 1 - D_u of the EMA warm-up.  Every word written here is read by LATER
@@ -273,10 +258,31 @@ __global__ __launch_bounds__(64) void sched_advance_kernel(double* __restrict__ 
     }
 }
 
-inline long step_grid(long n4) {
+// What every step entry point refuses alike (null, n <= 0 or no multiple of 4, a buffer off a 16-byte boundary), else the launch: one
+// float4 per lane, at most 4096 workgroups.  s1 is looked at only for a rule with two state buffers.
+template <class Rule, class Src>
+inline int launch_step(float* p, const float* g, float* s0, float* s1, long n, const Rule& rule, const Src& src, void* stream) {
+    if (!p || !g || !s0 || n <= 0 || (n & 3) || !al16(p) || !al16(g) || !al16(s0) || (Rule::kStates == 2 && (!s1 || !al16(s1))))
+        return RCOT_EINVAL;
+    const long n4 = n >> 2;
     long grid = (n4 + 255) / 256;
-    return grid > 4096 ? 4096 : grid;
+    if (grid > 4096) grid = 4096;
+    RCOT_LAUNCH((step_kernel<Rule, Src>), dim3((int)grid), dim3(256), 0, (hipStream_t)stream, (float4*)p, (const float4*)g, (float4*)s0,
+                (float4*)s1, n4, rule, src);
+    RCOT_LAUNCH_CHECK();
+    return RCOT_OK;
 }
+
+inline RmsProp rmsprop_rule(double alpha, double eps) { return {(float)alpha, (float)(1.0 - alpha), (float)eps}; }
+template <class Rule> inline Rule adam_rule(double b1, double b2, double eps) {
+    return {(float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), (float)eps};
+}
+// Adam's by-value scalars of step `step` >= 1: the bias corrections in double, as torch.optim forms them on the host
+inline ByValue adam_by_value(double lr, double b1, double b2, int step, double grad_scale, double weight_decay) {
+    const double bc1 = 1.0 - pow(b1, (double)step), bc2 = 1.0 - pow(b2, (double)step);
+    return {{(float)(lr / bc1), (float)(1.0 / sqrt(bc2)), (float)grad_scale, -(float)(lr * weight_decay)}};
+}
+inline bool ctrl_ok(const double* ctrl, int counter) { return ctrl && !(reinterpret_cast<uintptr_t>(ctrl) & 7) && counter >= 0 && counter <= 1; }
 
 // what rcot_ema_step and rcot_ema_step_dev refuse alike (false), else the form (float4 body + tail, or scalar) and the grid
 inline bool ema_geometry(const float* ema, const float* p, long n, int* vec, long* grid) {
@@ -301,30 +307,13 @@ extern "C" {
 // precision exactly as torch.optim does on the host (1 - 0.999f would be off by 1.3e-5 relative).
 int rcot_rmsprop_step(float* p, const float* g, float* sq, long n, double lr, double alpha, double eps,
                       double grad_scale, void* stream) {
-    if (!p || !g || !sq || n <= 0 || (n & 3) || !al16(p) || !al16(g) || !al16(sq)) return RCOT_EINVAL;
-    const long n4 = n >> 2;
-    long grid = (n4 + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    RCOT_LAUNCH(rmsprop_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, (float4*)p, (const float4*)g,
-                       (float4*)sq, n4, (float)lr, (float)alpha, (float)(1.0 - alpha), (float)eps, (float)grad_scale);
-    RCOT_LAUNCH_CHECK();
-    return RCOT_OK;
+    return launch_step(p, g, sq, nullptr, n, rmsprop_rule(alpha, eps), ByValue{{(float)lr, 0.f, (float)grad_scale, 0.f}}, stream);
 }
 
 int rcot_adam_step(float* p, const float* g, float* m, float* v, long n, double lr, double b1, double b2, double eps,
                    int step, double grad_scale, void* stream) {
-    if (!p || !g || !m || !v || n <= 0 || (n & 3) || step <= 0 || !al16(p) || !al16(g) || !al16(m) || !al16(v))
-        return RCOT_EINVAL;
-    const long n4 = n >> 2;
-    long grid = (n4 + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    const double bc1 = 1.0 - pow(b1, (double)step);
-    const double bc2 = 1.0 - pow(b2, (double)step);
-    RCOT_LAUNCH(adam_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, (float4*)p, (const float4*)g,
-                       (float4*)m, (float4*)v, n4, (float)lr, (float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2),
-                       (float)eps, (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), (float)grad_scale);
-    RCOT_LAUNCH_CHECK();
-    return RCOT_OK;
+    if (step <= 0) return RCOT_EINVAL;
+    return launch_step(p, g, m, v, n, adam_rule<Adam>(b1, b2, eps), adam_by_value(lr, b1, b2, step, grad_scale, 0.0), stream);
 }
 
 // 1 - decay is formed in double, as 1 - alpha above.  Any n >= 1 and any 4-byte-aligned pointers: float4 accesses when both are
@@ -354,16 +343,8 @@ int rcot_adamw_step(float* p, const float* g, float* m, float* v, long n, double
                     double grad_scale, double weight_decay, void* stream) {
     if (!(weight_decay >= 0.0)) return RCOT_EINVAL;                        // refuses NaN too
     if (weight_decay == 0.0) return rcot_adam_step(p, g, m, v, n, lr, b1, b2, eps, step, grad_scale, stream);
-    if (!p || !g || !m || !v || n <= 0 || (n & 3) || step <= 0 || !al16(p) || !al16(g) || !al16(m) || !al16(v))
-        return RCOT_EINVAL;
-    const long n4 = n >> 2;
-    const double bc1 = 1.0 - pow(b1, (double)step);
-    const double bc2 = 1.0 - pow(b2, (double)step);
-    RCOT_LAUNCH(adamw_kernel, dim3((int)step_grid(n4)), dim3(256), 0, (hipStream_t)stream, (float4*)p, (const float4*)g, (float4*)m,
-                (float4*)v, n4, (float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), (float)eps, (float)(lr / bc1),
-                (float)(1.0 / sqrt(bc2)), (float)grad_scale, -(float)(lr * weight_decay));
-    RCOT_LAUNCH_CHECK();
-    return RCOT_OK;
+    if (step <= 0) return RCOT_EINVAL;
+    return launch_step(p, g, m, v, n, adam_rule<AdamW>(b1, b2, eps), adam_by_value(lr, b1, b2, step, grad_scale, weight_decay), stream);
 }
 
 int rcot_sched_advance(double* sched, const double* table, int n_table, double* lr_dst0, double mult0, double* lr_dst1, double mult1,
@@ -402,39 +383,22 @@ int rcot_grad_decide(const double* partials, int nparts, double* ctrl, int flags
 }
 
 int rcot_rmsprop_step_guarded(float* p, const float* g, float* sq, long n, double alpha, double eps, const double* ctrl, void* stream) {
-    if (!p || !g || !sq || !ctrl || n <= 0 || (n & 3) || !al16(p) || !al16(g) || !al16(sq) || (reinterpret_cast<uintptr_t>(ctrl) & 7))
-        return RCOT_EINVAL;
-    const long n4 = n >> 2;
-    RCOT_LAUNCH(rmsprop_guarded_kernel, dim3((int)step_grid(n4)), dim3(256), 0, (hipStream_t)stream, (float4*)p, (const float4*)g,
-                (float4*)sq, n4, (float)alpha, (float)(1.0 - alpha), (float)eps, ctrl);
-    RCOT_LAUNCH_CHECK();
-    return RCOT_OK;
+    if (!ctrl_ok(ctrl, 0)) return RCOT_EINVAL;
+    return launch_step(p, g, sq, nullptr, n, rmsprop_rule(alpha, eps), FromCtrl{ctrl, 0, 0.0}, stream);
 }
 
 int rcot_adam_step_guarded(float* p, const float* g, float* m, float* v, long n, double b1, double b2, double eps, const double* ctrl,
                            int counter, void* stream) {
-    if (!p || !g || !m || !v || !ctrl || n <= 0 || (n & 3) || counter < 0 || counter > 1 || !al16(p) || !al16(g) || !al16(m) || !al16(v) ||
-        (reinterpret_cast<uintptr_t>(ctrl) & 7))
-        return RCOT_EINVAL;
-    const long n4 = n >> 2;
-    RCOT_LAUNCH(adam_guarded_kernel, dim3((int)step_grid(n4)), dim3(256), 0, (hipStream_t)stream, (float4*)p, (const float4*)g, (float4*)m,
-                (float4*)v, n4, (float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), (float)eps, ctrl, counter);
-    RCOT_LAUNCH_CHECK();
-    return RCOT_OK;
+    if (!ctrl_ok(ctrl, counter)) return RCOT_EINVAL;
+    return launch_step(p, g, m, v, n, adam_rule<Adam>(b1, b2, eps), FromCtrl{ctrl, counter, 0.0}, stream);
 }
 
 int rcot_adamw_step_guarded(float* p, const float* g, float* m, float* v, long n, double b1, double b2, double eps, const double* ctrl,
                             int counter, double weight_decay, void* stream) {
     if (!(weight_decay >= 0.0)) return RCOT_EINVAL;
     if (weight_decay == 0.0) return rcot_adam_step_guarded(p, g, m, v, n, b1, b2, eps, ctrl, counter, stream);
-    if (!p || !g || !m || !v || !ctrl || n <= 0 || (n & 3) || counter < 0 || counter > 1 || !al16(p) || !al16(g) || !al16(m) || !al16(v) ||
-        (reinterpret_cast<uintptr_t>(ctrl) & 7))
-        return RCOT_EINVAL;
-    const long n4 = n >> 2;
-    RCOT_LAUNCH(adamw_guarded_kernel, dim3((int)step_grid(n4)), dim3(256), 0, (hipStream_t)stream, (float4*)p, (const float4*)g, (float4*)m,
-                (float4*)v, n4, (float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), (float)eps, ctrl, counter, weight_decay);
-    RCOT_LAUNCH_CHECK();
-    return RCOT_OK;
+    if (!ctrl_ok(ctrl, counter)) return RCOT_EINVAL;
+    return launch_step(p, g, m, v, n, adam_rule<AdamW>(b1, b2, eps), FromCtrl{ctrl, counter, weight_decay}, stream);
 }
 
 }  // extern "C"

@@ -229,20 +229,13 @@ class PlannedMinimax:
         self.recordings = 0                      # plans recorded so far (a training run records one per batch shape / branch, not per step)
         self.warmup = warmup
         self._warmed = set()                     # (batch shape, arithmetic, spectral branch) that ran eagerly once
-        self.enabled = step.T.store.flat.is_cuda and hasattr(torch.cuda, "MemPool")
-        # the plain Adam / AdamW kernels take the step count BY VALUE (bias correction): not a static argument.  The guarded ones read it
-        # from their control block, where the decision launch advances it: nothing by-value changes between their iterations
-        if any(o.kind != "RMSprop" and getattr(o, "ctrl", None) is None for o in (step.To, step.Fo)):
-            self.enabled = False
+        # (an optimizer is not replayable when a by-value scalar of its launches changes every iteration)
+        self.enabled = step.T.store.flat.is_cuda and hasattr(torch.cuda, "MemPool") and step.To.replayable and step.Fo.replayable
 
     def _state_tensors(self):
         st = self.step
-        out = [st.T.store.flat, st.F.store.flat]
-        for o in (st.To, st.Fo):
-            out += list(o._state_tensors().values())
-            if getattr(o, "ctrl", None) is not None:    # a guarded optimizer's control block: the warm-up pass leaves no phantom counts
-                out.append(o.ctrl)
-        if st.ema is not None:                   # the warm-up pass must not leave a phantom update in the weight average either
+        out = [st.T.store.flat, st.F.store.flat] + st.To.restore_tensors() + st.Fo.restore_tensors()
+        if st.ema is not None:                  # the warm-up pass must not leave a phantom update in the weight average either
             out.append(st.ema.buf)
         if getattr(st, "schedule", None) is not None:    # nor a phantom advance in the schedule block
             out.append(st.schedule.block)
@@ -254,22 +247,9 @@ class PlannedMinimax:
         # the recorded calls when they change — _set_lr; rounds 4-5 keyed on them and re-recorded the iteration at every decay step)
         return (tuple(degraded.shape), bool(paired), bool(st._any_spectral), int(st.be.prec), st.grad_probe is not None)
 
-    def _lrs(self):
-        st = self.step
-        return (float(st.To.param_groups[0]["lr"]), float(st.Fo.param_groups[0]["lr"]))
-
     def _set_lr(self, ent):
         """bring the optimizer launches of a recorded iteration to the optimizers' current learning rates"""
-        lrs = self._lrs()
-        if ent["lr"] == lrs:
-            return
-        st = self.step
-        pT, pF = st.T.store.flat.data_ptr(), st.F.store.flat.data_ptr()
-        nT = ent["plan"].set_scalar("rcot_rmsprop_step", 4, lrs[0], where=lambda a: a[0] == pT)
-        nF = ent["plan"].set_scalar("rcot_rmsprop_step", 4, lrs[1], where=lambda a: a[0] == pF)
-        if nT != ent["n_opt"][0] or nF != ent["n_opt"][1]:
-            raise RuntimeError(f"launch plan: {nT} + {nF} optimizer launches found, {ent['n_opt']} recorded")
-        ent["lr"] = lrs
+        ent["lr"] = tuple(o.plan_set_lr(ent["plan"], noted) for o, noted in zip((self.step.To, self.step.Fo), ent["lr"]))
 
     def _sync_packs(self):
         """A recorded iteration starts with kernels that read the weight packs of ITS arithmetic and ends with the launch that
@@ -345,10 +325,7 @@ class PlannedMinimax:
             warnings.warn(f"rcot_amd.plan: {self.recordings} launch plans recorded so far — the iteration's configuration (batch shape, "
                           "paired / spectral branch, arithmetic) keeps changing, or RCOT_PLAN_CACHE is too small; every recording costs "
                           "an eager iteration plus a device synchronisation (RCOT_PLAN=0 walks the schedule instead)")
-        pT, pF = st.T.store.flat.data_ptr(), st.F.store.flat.data_ptr()
-        n_opt = tuple(sum(1 for fn, a_, _s in plan.cmds if a_ is not None and getattr(fn, "__name__", "") == "rcot_rmsprop_step" and a_[0] == q)
-                      for q in (pT, pF))
-        return dict(plan=plan, x=x, y=y, d=d, a=a, out=box["out"], logs=dict(st.logs), lr=self._lrs(), n_opt=n_opt)
+        return dict(plan=plan, x=x, y=y, d=d, a=a, out=box["out"], logs=dict(st.logs), lr=(st.To.plan_note(plan), st.Fo.plan_note(plan)))
 
     def iteration(self, degraded, target, de_id, alpha, paired: bool):
         st = self.step

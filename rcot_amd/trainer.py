@@ -318,6 +318,41 @@ class FlatOptimizer:
             self.ctrl[_lib.CB_LR:_lib.CB_LR + 1].fill_(lr)
             self._lr_written = lr
 
+    # ---- launch plans (rcot_amd/plan.py): how this optimizer's per-iteration scalars reach its launches decides what a plan may do
+    # Without a control block the learning rate is argument _LR_ARG of the _LR_ENTRY launches whose first argument is this flat buffer.
+    _LR_ENTRY, _LR_ARG = "rcot_rmsprop_step", 4
+
+    @property
+    def replayable(self) -> bool:
+        """Whether a recorded iteration that holds this optimizer's steps can be replayed.  Not plain Adam / AdamW: their launches take
+        the step count BY VALUE (bias correction).  The guarded ones read rate, counts and bias corrections from the control block,
+        where the decision launch advances them, and plain RMSprop's only changing scalar is the rate, which plan_set_lr patches."""
+        return self.kind == "RMSprop" or self.ctrl is not None
+
+    def restore_tensors(self):
+        """what a warm-up pass that must not count as an iteration puts back: the state and, when guarded, the control block (no
+        phantom counts)"""
+        return list(self._state_tensors().values()) + ([self.ctrl] if self.ctrl is not None else [])
+
+    def plan_note(self, plan):
+        """Called once ``plan`` (a LaunchPlan) holds a recorded iteration: (the number of this optimizer's launches in it that carry the
+        rate by value, that rate) — what plan_set_lr is handed at every later replay.  A guarded optimizer has none: sync_lr serves it."""
+        flat = self.net.store.flat.data_ptr()
+        n = sum(1 for fn, a, _side in plan.cmds if a is not None and getattr(fn, "__name__", "") == self._LR_ENTRY and a[0] == flat)
+        return n, float(self.param_groups[0]["lr"])
+
+    def plan_set_lr(self, plan, noted):
+        """bring the launches counted by plan_note to ``param_groups[0]["lr"]``; returns the new note"""
+        n, lr_then = noted
+        lr = float(self.param_groups[0]["lr"])
+        if lr == lr_then:
+            return noted
+        flat = self.net.store.flat.data_ptr()
+        found = plan.set_scalar(self._LR_ENTRY, self._LR_ARG, lr, where=lambda a: a[0] == flat)
+        if found != n:
+            raise RuntimeError(f"launch plan: {found} optimizer launches found, {n} recorded")
+        return n, lr
+
     def step(self, n_live: Optional[int] = None, same_batch: bool = False):
         """Update params[0:n_live) (default: every live parameter).  A shorter range reproduces
         autograd's 'grad is None -> skipped' for the trailing tensors (fc2.bias in the GP step).

@@ -1,7 +1,7 @@
 # rocprofv3 --kernel-trace --stats of `bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-roofline $BENCH_ARGS` -> gpurun_out/kstats${TAG}.txt
 # Round 5: the statistics cover the REPLAYED iterations only.  The process runs 2 + 1 + 8 + 1 iterations: the eager warm-up pass and
 # the recording pass of the launch plan (both inside the first warm-up call), one warm-up replay, 8 timed replays, one host-enqueue
-# probe.  An iteration ends with its third optimizer launch (rmsprop_kernel: critic, gradient penalty, generator); every dispatch that
+# probe.  An iteration ends with its third optimizer launch (an instantiation of optim.hip's step_kernel: critic, gradient penalty, generator); every dispatch that
 # starts after the sixth one is a replayed launch.  Per-step figures = totals / replayed iterations.
 cd /tmp && export TMPDIR=/tmp
 rm -rf $GRAFT_REPO_ROOT/gpurun_out/prof${TAG}
@@ -13,7 +13,7 @@ tag = os.environ.get("TAG", "")
 db = sorted(glob.glob(f"gpurun_out/prof{tag}/**/*.db", recursive=True))[-1]
 c = sqlite3.connect(db)
 rows = c.execute("select name, start, end from kernels order by start").fetchall()
-opt = [r for r in rows if "rmsprop_kernel" in r[0] or "adam_kernel" in r[0]]
+opt = [r for r in rows if "::step_kernel<" in r[0]]
 assert len(opt) >= 9 and len(opt) % 3 == 0, len(opt)
 t0 = opt[5][2]                                   # end of the recording pass's last optimizer launch
 iters = len(opt) // 3 - 2

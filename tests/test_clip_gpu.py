@@ -274,7 +274,7 @@ def test_refusals_launch_nothing():
     p, g, (m, v) = _opt_buffers(gs, n, 17, True)
     blk = _Block(gs, 1.0)
     blk.partials.fill_(float("nan"))
-    c0, p0 = blk.ctrl.clone(), p.clone()
+    c0, p0, state0 = blk.ctrl.clone(), p.clone(), (g.clone(), m.clone(), v.clone())
     L, st = be.L, be._st()
     P_, G, M_, V, C, W = (t.data_ptr() for t in (p, g, m, v, blk.ctrl, blk.partials))
     cases = [L.rcot_grad_sumsq(0, n, W, st), L.rcot_grad_sumsq(G, 0, W, st), L.rcot_grad_sumsq(G, n, 0, st), L.rcot_grad_sumsq(G + 2, n - 1, W, st),
@@ -285,9 +285,16 @@ def test_refusals_launch_nothing():
              L.rcot_rmsprop_step_guarded(P_, G, M_, n, 0.99, 1e-8, 0, st), L.rcot_adam_step_guarded(P_, G, M_, V, n, 0.9, 0.999, 1e-8, C, 2, st),
              L.rcot_adam_step_guarded(P_, G, M_, V, n, 0.9, 0.999, 1e-8, C, -1, st), L.rcot_adam_step_guarded(P_, G, M_, 0, n, 0.9, 0.999, 1e-8, C, 0, st),
              L.rcot_adam_step_guarded(P_, G, M_, V, n + 2, 0.9, 0.999, 1e-8, C, 0, st), L.rcot_adam_step_guarded(P_, G + 8, M_, V, n - 4, 0.9, 0.999, 1e-8, C, 0, st)]
+    # the two plain steps refuse alike: a null pointer, n = 0, n = 6 (no multiple of 4), a pointer 4 bytes off, and for Adam step = 0
+    rms = lambda p_=P_, g_=G, s_=M_, n_=n: L.rcot_rmsprop_step(p_, g_, s_, n_, 1e-3, 0.99, 1e-8, 1.0, st)
+    adam = lambda p_=P_, g_=G, m_=M_, v_=V, n_=n, t=1: L.rcot_adam_step(p_, g_, m_, v_, n_, 1e-3, 0.9, 0.999, 1e-8, t, 1.0, st)
+    cases += [rms(p_=0), rms(g_=0), rms(s_=0), rms(n_=0), rms(n_=6), rms(p_=P_ + 4, n_=n - 4), rms(g_=G + 4, n_=n - 4), rms(s_=M_ + 4, n_=n - 4),
+              adam(p_=0), adam(g_=0), adam(m_=0), adam(v_=0), adam(n_=0), adam(n_=6), adam(p_=P_ + 4, n_=n - 4), adam(g_=G + 4, n_=n - 4),
+              adam(m_=M_ + 4, n_=n - 4), adam(v_=V + 4, n_=n - 4), adam(t=0)]
     assert cases == [EINVAL] * len(cases), cases
     gs.check()
     assert _same_bits(blk.ctrl, c0) and _same_bits(p, p0) and bool(torch.isnan(blk.partials).all())
+    assert all(_same_bits(a, b) for a, b in zip((g, m, v), state0))
     assert L.rcot_grad_sumsq_parts(0) == 0 and L.rcot_grad_sumsq_parts(3) == 1 and L.rcot_grad_sumsq_parts(BIG) == 4096
 
 
